@@ -9,13 +9,20 @@ contains only the kernel launches.  Multi-GPU: one process per GPU, each
 processing its own shard (packets are independent: weak scaling, no
 data-path collective).
 
-Beside `value` (never inside it), rank 0 at N=1 reports legs: the same burst
+A plain run sets up, warms up, times the K steps and prints the result line.
+With --full, beside `value` (never inside it), it also reports the roofline of
+the pipeline kernel alone, and rank 0 at N=1 reports legs: the same burst
 with meta records, with a flow table attached (flow_table), port forwarding
 and masquerade under load (nat_portfw, nat_masquerade: a share of a 2M burst
 opening new stateful-NAT connections; nat_mixed: both on one public range),
 host-origin bursts (host_inclusive), and the CPU baseline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2]
+--dump-outputs DIR writes what the last timed step handed back (see
+dump_outputs) as DIR/<name>.npy; the inputs are a function of the arguments
+alone, so two builds can be compared output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2] [--full]
+                    [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -37,6 +44,9 @@ from dataplane_amd.workload import ALGO_BYTES, CONFIG_NAMES, Workload  # noqa: E
 
 METRIC = "Mpps device-resident (64B IPv4, 1M-route LPM + 10k ACL + NAT) at 1/2/4/8 GPU"
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md chip table (spec)
+STAGED_BYTES = 32 << 30  # HBM for the pre-staged bursts of the timed steps
+DUMP_SAMPLE = 65536  # packets whose records and frames --dump-outputs writes
+DUMP_FRAME = 128  # bytes of each sampled frame (64 B frames, C4's encapsulated ones: 114 B)
 
 
 def log(rank, *a):
@@ -53,6 +63,38 @@ def measured_traffic(cfg: int, n: int):
     except (OSError, KeyError, ValueError):
         return None, None
     return int(t["bytes_per_pkt"] * n), t["source"]
+
+
+def dump_outputs(path: str, seed: int, buf: np.ndarray, nbytes: int, out: np.ndarray,
+                 stats: np.ndarray) -> None:
+    """What a caller of the timed path holds after the last timed step, as
+    float .npy files under `path` (about 45 MB at 2M packets):
+      done.npy           float32 [n]      every packet's DoneReason
+      sample_index.npy   float64 [s]      a fixed sample of packets (a function of
+                                          `seed` and n alone, ascending)
+      sample_out.npy     float64 [s, 6]   their dp_pkt_out_t records: off, len, done,
+                                          acl, oif, meta_flags
+      sample_frames.npy  float32 [s, 128] the first bytes of their frames as
+                                          serialized in the burst buffer at
+                                          (off, len), zero past len; all zero for
+                                          a packet that was not delivered (its
+                                          buffer is released, its bytes unspecified)
+      stats.npy          float64 [DONE_COUNT] the DoneReason histogram the timed
+                                          steps accumulated in the stats array"""
+    os.makedirs(path, exist_ok=True)
+    n = len(out)
+    idx = np.sort(np.random.default_rng(seed).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    so = out[idx]
+    rec = np.stack([so[f].astype(np.float64) for f in ("off", "len", "done", "acl", "oif",
+                                                       "meta_flags")], axis=1)
+    col = np.arange(DUMP_FRAME, dtype=np.int64)[None, :]
+    pos = np.minimum(so["off"].astype(np.int64)[:, None] + col, nbytes - 1)
+    keep = (col < so["len"].astype(np.int64)[:, None]) & (so["done"] == A.DONE["Delivered"])[:, None]
+    frames = np.where(keep, buf[pos], 0).astype(np.float32)
+    for name, a in (("done", out["done"].astype(np.float32)), ("sample_index", idx.astype(np.float64)),
+                    ("sample_out", rec), ("sample_frames", frames),
+                    ("stats", stats.astype(np.float64))):
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_model() -> str:
@@ -546,6 +588,17 @@ def main() -> None:
                          "frames) or packed (96 B headroom, 16-byte aligned)")
     ap.add_argument("--nat-kind", choices=["both", "pf", "masq", "mixed"], default="both",
                     help="with --nat-only: which NAT legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything measured beside the headline value: the roofline and "
+                         "with-meta launches, the flow-table, NAT and host-origin legs, the CPU "
+                         "baseline, and at N > 1 the resident-burst scatter / gather (each still "
+                         "subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank "
+                         "0's shard) as DIR/<name>.npy")
+    ap.add_argument("--staged-bytes", type=int, default=STAGED_BYTES,
+                    help="HBM for the pre-staged bursts of the timed steps; more steps than fit "
+                         "run in chunks, the bursts renewed untimed between chunks")
     ap.add_argument("--launch-probe", action="store_true",
                     help="test hook: each rank prints its rank / world as JSON and exits before "
                          "any GPU call")
@@ -553,6 +606,8 @@ def main() -> None:
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: start the N ranks ourselves (before any GPU call)
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -599,11 +654,13 @@ def main() -> None:
 
     n = w.n
     bb = (w.buf.nbytes + 255) & ~255
-    nbuf = args.warmup + args.steps
+    # the staged bursts: one pristine copy per step, at most --staged-bytes of
+    # them; more steps than that run in chunks, the copies renewed (untimed)
+    # between chunks
+    nbuf = max(1, min(max(args.warmup, args.steps), args.staged_bytes // bb))
+    chunks = [min(nbuf, args.steps - s) for s in range(0, args.steps, nbuf)]
     pristine = torch.from_numpy(w.buf).to(dev)
     bufs = torch.empty((nbuf, bb), dtype=torch.uint8, device=dev)
-    for k in range(nbuf):
-        bufs[k, :w.buf.nbytes].copy_(pristine)
     dinp = torch.from_numpy(w.inp.view(np.uint8)).to(dev)
     dout = torch.empty(n * A.PKT_OUT.itemsize, dtype=torch.uint8, device=dev)
     dstats = torch.zeros(A.DONE_COUNT, dtype=torch.int64, device=dev)
@@ -612,64 +669,79 @@ def main() -> None:
     # context's own stream)
     stream = torch.cuda.Stream(dev)
     sptr = stream.cuda_stream
-    torch.cuda.synchronize(dev)
+
+    def restage(count):
+        for k in range(count):
+            bufs[k, :w.buf.nbytes].copy_(pristine)
+        torch.cuda.synchronize(dev)
 
     def step(k):
         nf.process_device(bufs[k].data_ptr(), bb, dinp.data_ptr(), dout.data_ptr(), n,
                           dstats.data_ptr(), sptr)
 
-    for k in range(args.warmup):
-        step(k)
-    torch.cuda.synchronize(dev)
+    for s in range(0, args.warmup, nbuf):
+        c = min(nbuf, args.warmup - s)
+        restage(c)
+        for k in range(c):
+            step(k)
+        torch.cuda.synchronize(dev)
     dstats.zero_()
     # one event per step boundary, on the launch stream: per-step durations
     # (median) besides the whole timed region
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    barrier()
-    torch.cuda.synchronize(dev)
-    t_start = time.perf_counter()
-    evs[0].record(stream)
-    for k in range(args.steps):
-        step(args.warmup + k)
-        evs[k + 1].record(stream)
-    torch.cuda.synchronize(dev)
-    barrier()
-    elapsed = time.perf_counter() - t_start
-    step_ms = [evs[k].elapsed_time(evs[k + 1]) for k in range(args.steps)]
-    kernel_ms = evs[0].elapsed_time(evs[-1]) / args.steps
+    elapsed, events_ms, step_ms, last = 0.0, 0.0, [], 0
+    for ci, c in enumerate(chunks):
+        restage(c)
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(c + 1)]
+        if ci == 0:
+            barrier()
+        torch.cuda.synchronize(dev)
+        t_start = time.perf_counter()
+        evs[0].record(stream)
+        for k in range(c):
+            step(k)
+            evs[k + 1].record(stream)
+        torch.cuda.synchronize(dev)
+        if ci == len(chunks) - 1:
+            barrier()
+        elapsed += time.perf_counter() - t_start
+        step_ms += [evs[k].elapsed_time(evs[k + 1]) for k in range(c)]
+        events_ms += evs[0].elapsed_time(evs[-1])
+        last = c - 1
+    kernel_ms = events_ms / args.steps
 
-    # roofline timing of dp_pipeline_kernel alone (no histogram, so no
-    # dp_stats_reduce launch): one event pair per launch, re-using the
-    # processed buffers' pristine copies
-    for k in range(nbuf):
-        bufs[k, :w.buf.nbytes].copy_(pristine)
-    torch.cuda.synchronize(dev)
-    kev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-           for _ in range(args.steps)]
-    for k in range(args.steps):
-        kev[k][0].record(stream)
-        nf.process_device(bufs[args.warmup + k].data_ptr(), bb, dinp.data_ptr(), dout.data_ptr(), n,
-                          None, sptr)
-        kev[k][1].record(stream)
-    torch.cuda.synchronize(dev)
-    launch_ms = sorted(a.elapsed_time(b) for a, b in kev)
-    pipe_ms_median = launch_ms[len(launch_ms) // 2]
-    pipe_ms_mean = sum(launch_ms) / len(launch_ms)
-    # the same launches also writing the optional dp_pkt_meta_t array (the
-    # rest of PacketMeta: VNIs, FIB entry, ACL rule, VRF, next hop, DSCP)
-    dmeta = torch.empty(n * A.PKT_META.itemsize, dtype=torch.uint8, device=dev)
-    for k in range(nbuf):
-        bufs[k, :w.buf.nbytes].copy_(pristine)
-    torch.cuda.synchronize(dev)
-    for k in range(args.steps):
-        kev[k][0].record(stream)
-        nf.process_device(bufs[args.warmup + k].data_ptr(), bb, dinp.data_ptr(), dout.data_ptr(), n,
-                          None, sptr, dev_meta=dmeta.data_ptr())
-        kev[k][1].record(stream)
-    torch.cuda.synchronize(dev)
-    meta_ms = sorted(a.elapsed_time(b) for a, b in kev)
-    meta_ms_median = meta_ms[len(meta_ms) // 2]
-    del dmeta
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, args.seed, bufs[last].cpu().numpy(), w.buf.nbytes,
+                     dout.cpu().numpy().view(A.PKT_OUT), dstats.cpu().numpy())
+
+    def launch_ms(**kw):
+        """Sorted HIP-event times of args.steps launches without the
+        histogram (so no dp_stats_reduce launch), one event pair per launch,
+        each on a pristine burst."""
+        ms = []
+        for c in chunks:
+            restage(c)
+            kev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+                   for _ in range(c)]
+            for k in range(c):
+                kev[k][0].record(stream)
+                nf.process_device(bufs[k].data_ptr(), bb, dinp.data_ptr(), dout.data_ptr(), n,
+                                  None, sptr, **kw)
+                kev[k][1].record(stream)
+            torch.cuda.synchronize(dev)
+            ms += [a.elapsed_time(b) for a, b in kev]
+        return sorted(ms)
+
+    if args.full:
+        # roofline timing of dp_pipeline_kernel alone
+        pipe_ms = launch_ms()
+        pipe_ms_median = pipe_ms[len(pipe_ms) // 2]
+        pipe_ms_mean = sum(pipe_ms) / len(pipe_ms)
+        # the same launches also writing the optional dp_pkt_meta_t array (the
+        # rest of PacketMeta: VNIs, FIB entry, ACL rule, VRF, next hop, DSCP)
+        dmeta = torch.empty(n * A.PKT_META.itemsize, dtype=torch.uint8, device=dev)
+        meta_ms = launch_ms(dev_meta=dmeta.data_ptr())
+        meta_ms_median = meta_ms[len(meta_ms) // 2]
+        del dmeta
 
     elapsed, hist = reduce_over_ranks(elapsed, dstats.cpu().numpy(), dev)
 
@@ -677,7 +749,7 @@ def main() -> None:
     # (rank 0's shard scattered over all ranks with RCCL point-to-point sends,
     # processed, gathered back), reported beside -- never inside -- `value`
     rccl = None
-    if world > 1 and not args.no_rccl:
+    if args.full and world > 1 and not args.no_rccl:
         del bufs
         w0 = w if rank == 0 else Workload(cfg, args.packets, seed=shard_seed(args.seed, 0),
                                           n_routes_v4=args.routes_v4, n_routes_v6=args.routes_v6,
@@ -702,19 +774,6 @@ def main() -> None:
 
     result = None
     if rank == 0:
-        achieved = n * ALGO_BYTES[cfg] / (pipe_ms_mean / 1e3) / 1e9
-        traffic, traffic_src = measured_traffic(cfg, n)
-        roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
-                    "kernel": "dp_pipeline_kernel", "kernel_ms": round(pipe_ms_mean, 4),
-                    "kernel_ms_median": round(pipe_ms_median, 4),
-                    "kernel_timing": f"HIP events around each of {args.steps} launches on the "
-                                     "launch stream (achieved uses the mean, as rocprof's "
-                                     "AverageNs)",
-                    "bytes_per_pkt": ALGO_BYTES[cfg]}
-        if traffic is not None:
-            roofline["traffic_unit"] = "bytes per launch"
-            roofline["traffic_source"] = traffic_src
         result = {
             "metric": METRIC, "value": round(value, 3), "unit": "Mpps", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
@@ -730,22 +789,37 @@ def main() -> None:
             "step_ms_median": round(sorted(step_ms)[len(step_ms) // 2], 4),
             "step_ms_events_mean": round(kernel_ms, 4),
             "mpps_median_step": round(world * n / (sorted(step_ms)[len(step_ms) // 2] / 1e3) / 1e6, 3),
-            "roofline": roofline,
-            "with_meta": {"kernel_ms_median": round(meta_ms_median, 4),
-                          "mpps_median": round(n / (meta_ms_median / 1e3) / 1e6, 3),
-                          "what": "the same launches also writing dp_pkt_meta_t (48 B per "
-                                  "packet: the rest of PacketMeta) beside dp_pkt_out_t"},
             "done_histogram": {A.DONE_NAMES[i]: int(c) for i, c in enumerate(hist) if c},
         }
+        if args.full:
+            achieved = n * ALGO_BYTES[cfg] / (pipe_ms_mean / 1e3) / 1e9
+            traffic, traffic_src = measured_traffic(cfg, n)
+            roofline = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
+                        "kernel": "dp_pipeline_kernel", "kernel_ms": round(pipe_ms_mean, 4),
+                        "kernel_ms_median": round(pipe_ms_median, 4),
+                        "kernel_timing": f"HIP events around each of {args.steps} launches on the "
+                                         "launch stream (achieved uses the mean, as rocprof's "
+                                         "AverageNs)",
+                        "bytes_per_pkt": ALGO_BYTES[cfg]}
+            if traffic is not None:
+                roofline["traffic_unit"] = "bytes per launch"
+                roofline["traffic_source"] = traffic_src
+            result["roofline"] = roofline
+            result["with_meta"] = {"kernel_ms_median": round(meta_ms_median, 4),
+                                   "mpps_median": round(n / (meta_ms_median / 1e3) / 1e6, 3),
+                                   "what": "the same launches also writing dp_pkt_meta_t (48 B per "
+                                           "packet: the rest of PacketMeta) beside dp_pkt_out_t"}
         if rccl:
             result["resident_burst_scatter_gather"] = rccl
-        if world == 1 and not args.no_flows:
+        legs = args.full and world == 1  # the legs beside `value`: rank 0 at N=1
+        if legs and not args.no_flows:
             result["flow_table"] = flows_leg(nf, w, dev, stream, args.steps)
-        if world == 1 and not args.no_nat:
+        if legs and not args.no_nat:
             result["nat_portfw"] = nat_leg(dev, stream, min(args.steps, 10), n)
             result["nat_masquerade"] = nat_leg(dev, stream, min(args.steps, 10), n, kind="masq")
             result["nat_mixed"] = nat_leg(dev, stream, min(args.steps, 10), n, kind="mixed")
-        if world == 1 and not args.no_host:
+        if legs and not args.no_host:
             # host-origin rate (dp_process_burst): pinned host burst buffer and
             # records, chunked H2D / kernel / D2H overlapped on several streams
             def pinned(nbytes):
@@ -793,7 +867,7 @@ def main() -> None:
             best = max(host["mpps_median"], host.get("zero_copy", {}).get("mpps_median", 0))
             result["host_inclusive_mpps"] = best
             result["host_inclusive"] = host
-        if world == 1 and not args.no_cpu:
+        if legs and not args.no_cpu:
             result["cpu_baseline"] = cpu_baseline(w, args.cpu_sample, args.cpu_budget)
         print(json.dumps(result), flush=True)
     nf.close()

@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_DIR = os.path.join(HERE, "lib")
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 HEADROOM = 96
 
 # DoneReason (net/src/packet/meta.rs:84-119)
@@ -265,7 +265,8 @@ GPU_SYMBOLS = ["dp_abi_version", "dp_ctx_create", "dp_ctx_destroy", "dp_tables_p
                "dp_ctx_attach_flow_table", "dp_mbuf_burst_in", "dp_mbuf_burst_out",
                "dp_process_mbufs", "dp_acl_classify", "dp_acl_classify_device",
                "dp_acl_key_from_match", "dp_acl_classify_match", "dp_ff_classify",
-               "dp_ff_classify_device", "dp_ff_key_from_match", "dp_ff_classify_match"]
+               "dp_ff_classify_device", "dp_ff_key_from_match", "dp_ff_classify_match",
+               "dp_vpc_stats_accumulate_device", "dp_vpc_stats_read"]
 # dp_acl_key_t / dp_acl_result_t (the ACL classifier alone)
 ACL_KEY = np.dtype([("src_vni", "<u4"), ("dst_vni", "<u4"), ("family", "u1"), ("proto", "u1"),
                     ("sport", "<u2"), ("dport", "<u2"), ("pad", "u1", 2), ("src", "u1", 16),
@@ -284,8 +285,15 @@ FF_DESTINATION_MISS, FF_SOURCE_MISS, FF_ROUTE = 0, 1, 2
 FF_REMOTE, FF_LOCAL = 1, 2
 # the reference's RemoteKey / LocalKey bytes (MatchKey::as_key_into; dp_ff_key_from_match)
 FF_REMOTE_KEY_V4, FF_REMOTE_KEY_V6, FF_LOCAL_KEY_V4, FF_LOCAL_KEY_V6 = 15, 27, 16, 28
+# dp_vpc_stat_t (per-VPC statistics: the Stats stage, stats/src/dpstats.rs:914-1011);
+# dst_vni 0: the source VPC's drop total
+VPC_STAT = np.dtype([("src_vni", "<u4"), ("dst_vni", "<u4"), ("fwd_packets", "<u8"), ("fwd_bytes", "<u8"),
+                     ("drop_packets", "<u8"), ("drop_bytes", "<u8")])
+VPC_STATS_CELLS = 4096  # DP_VPC_STATS_CELLS
+ENOSPC = -28
 NP_STRUCTS = dict(dp_flow_key_t=FLOW_KEY, dp_flow_t=FLOW, dp_flow_info_t=FLOW_INFO, dp_acl_key_t=ACL_KEY,
-                  dp_acl_result_t=ACL_RESULT, dp_ff_input_t=FF_INPUT, dp_ff_result_t=FF_RESULT)
+                  dp_acl_result_t=ACL_RESULT, dp_ff_input_t=FF_INPUT, dp_ff_result_t=FF_RESULT,
+                  dp_vpc_stat_t=VPC_STAT)
 
 
 class MbufLayout(C.Structure):
@@ -300,6 +308,7 @@ MBUF_LAYOUT_DPDK = MbufLayout(0, 16, 20, 22, 36, 40, 54, 0)  # DP_MBUF_LAYOUT_DP
 # dp_ctx_set_option (include/dpgpu.h)
 OPT_HOST_PATH = 1
 OPT_CLOCK = 2
+OPT_VPC_STATS = 3
 HOST_AUTO, HOST_COPY, HOST_ZERO_COPY = 0, 1, 2
 
 _VP = C.c_void_p
@@ -392,6 +401,9 @@ def gpu_lib() -> C.CDLL:
         lib.dp_ff_classify_device.argtypes = [_VP, _VP, _VP, C.c_uint32, _VP]
         lib.dp_ff_key_from_match.argtypes = [C.c_int, _VP, C.c_uint32, C.c_uint32, C.c_uint32, _VP]
         lib.dp_ff_classify_match.argtypes = [_VP, C.c_int, _VP, C.c_uint32, C.c_uint32, C.c_uint32, _VP]
+        lib.dp_vpc_stats_accumulate_device.argtypes = [_VP, _VP, _VP, C.c_uint32, _VP]
+        lib.dp_vpc_stats_read.argtypes = [_VP, _VP, C.c_uint32, C.POINTER(C.c_uint32),
+                                          C.POINTER(C.c_uint64), C.c_int]
         lib.dpd_debug_classify_copies.argtypes = [C.c_int]
         lib.dpd_debug_hip_runtimes.restype = C.c_int
         lib.dpf_debug_nat_sequential.argtypes = [C.c_int]

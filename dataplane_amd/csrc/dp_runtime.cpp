@@ -35,7 +35,10 @@
 #include "../../include/dpgpu.h"
 #include "dp_flows_rt.h"
 #include "dp_tables.h"
+#include "dp_vpcstats.h"
 
+extern "C" int dpk_vpc_stats(const dp_pkt_out_t *out, const dp_pkt_meta_t *meta, uint32_t n, void *table,
+                             uint32_t max_blocks, hipStream_t stream);
 extern "C" int dpk_launch_pipeline(const uint8_t *img_base, const void *image_dev, uint8_t *buf,
                                    uint64_t buf_bytes, const dp_pkt_in_t *in, dp_pkt_out_t *out,
                                    dp_pkt_meta_t *meta, uint32_t n, uint64_t *stats, uint64_t *stats_part,
@@ -283,6 +286,17 @@ struct dp_ctx {
   hipEvent_t side_fork = nullptr, side_fork2 = nullptr, side_join = nullptr;
   bool side_tried = false;
   uint64_t clock = 0;                  // dp_ctx_set_option(DP_OPT_CLOCK)
+  // per-VPC statistics (DP_OPT_VPC_STATS; allocated at the first use): the
+  // device table, its pinned copy for dp_vpc_stats_read, the launch's
+  // workgroups, and the meta scratch of bursts without a meta array -- one
+  // array, so a burst waits for the previous one that used it
+  bool vpc_stats = false;
+  dpv::Table *vs_tab = nullptr, *vs_host = nullptr;
+  uint32_t vs_blocks = 0;
+  dp_pkt_meta_t *vs_meta = nullptr;
+  uint32_t vs_meta_cap = 0;
+  hipEvent_t vs_used = nullptr;
+  bool vs_armed = false;
   // host threads of the staged-copy path, the context's own: a staged burst
   // waits for its own chunks only, never for another worker's
   std::unique_ptr<HostPool> pool;
@@ -476,6 +490,43 @@ void mark_failed_host(const dp_pkt_in_t *in, dp_pkt_out_t *out, dp_pkt_meta_t *m
   }
 }
 
+// The context's statistics table and its launch geometry, at the first use.
+int vs_ensure(dp_ctx *c) {
+  if (c->vs_tab) return 0;
+  hipError_t e;
+  int cus = 0;
+  if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device)) != hipSuccess || cus <= 0)
+    return fail(DP_EIO, "compute unit count", e);
+  dpv::Table *tab = nullptr, *host = nullptr;
+  if ((e = hipMalloc(&tab, sizeof(dpv::Table))) != hipSuccess ||
+      (e = hipHostMalloc(&host, sizeof(dpv::Table))) != hipSuccess ||
+      (e = hipMemset(tab, 0, sizeof(dpv::Table))) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&c->vs_used, hipEventDisableTiming)) != hipSuccess) {
+    if (tab) (void)hipFree(tab);
+    if (host) (void)hipHostFree(host);
+    return fail(DP_ENOMEM, "per-VPC statistics table", e);
+  }
+  c->vs_tab = tab;
+  c->vs_host = host;
+  c->vs_blocks = (uint32_t)cus * dpv::kBlocksPerCu;
+  return 0;
+}
+
+// The meta scratch of a statistics burst without a meta array, for n packets,
+// ordered on `s` behind the burst that used it last.
+dp_pkt_meta_t *vs_scratch(dp_ctx *c, uint32_t n, hipStream_t s) {
+  if (n > c->vs_meta_cap) {
+    if (c->vs_armed) (void)hipEventSynchronize(c->vs_used);
+    if (c->vs_meta) (void)hipFree(c->vs_meta);
+    c->vs_meta = nullptr;
+    c->vs_meta_cap = 0;
+    if (hipMalloc(&c->vs_meta, sizeof(dp_pkt_meta_t) * (size_t)n) != hipSuccess) return nullptr;
+    c->vs_meta_cap = n;
+  }
+  if (c->vs_armed && hipStreamWaitEvent(s, c->vs_used, 0) != hipSuccess) return nullptr;
+  return c->vs_meta;
+}
+
 }  // namespace
 
 extern "C" {
@@ -565,6 +616,10 @@ int dp_ctx_destroy(dp_ctx_t *c) {
   if (c->mb_out) (void)hipHostFree(c->mb_out);
   if (c->mb_meta) (void)hipHostFree(c->mb_meta);
   if (c->fl_used) (void)hipEventDestroy(c->fl_used);
+  if (c->vs_used) { (void)hipEventSynchronize(c->vs_used); (void)hipEventDestroy(c->vs_used); }
+  if (c->vs_tab) (void)hipFree(c->vs_tab);
+  if (c->vs_host) (void)hipHostFree(c->vs_host);
+  if (c->vs_meta) (void)hipFree(c->vs_meta);
   if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
   if (c->side_fork) (void)hipEventDestroy(c->side_fork);
   if (c->side_fork2) (void)hipEventDestroy(c->side_fork2);
@@ -666,6 +721,31 @@ static int launch_burst(dp_ctx_t *c, uint8_t *dev_buf, uint64_t buf_bytes, const
     (void)dpk_mark_failed(dev_in, dev_out, dev_meta, n, s);
     return !img ? fail(DP_ENOTABLES, "no tables published") : fail(DP_EINVAL, "bad burst buffer");
   }
+  // per-VPC statistics: the stage reads the burst's meta records, the
+  // context's scratch where the caller passes no array
+  bool vs_own_meta = false;
+  if (c->vpc_stats) {
+    int vrc = vs_ensure(c);
+    if (!vrc && !dev_meta) {
+      vs_own_meta = true;
+      if (!(dev_meta = vs_scratch(c, n, s))) vrc = fail(DP_ENOMEM, "per-VPC statistics meta scratch");
+    }
+    if (vrc) {
+      (void)dpk_mark_failed(dev_in, dev_out, vs_own_meta ? nullptr : dev_meta, n, s);
+      return vrc;
+    }
+  }
+  // whatever this call still enqueues on `s` may write the scratch (the
+  // kernels, or dpk_mark_failed on a failure): the next burst that takes it
+  // waits for all of it, on every way out
+  struct ScratchUse {
+    dp_ctx *c;
+    hipStream_t s;
+    bool on;
+    ~ScratchUse() {
+      if (on && hipEventRecord(c->vs_used, s) == hipSuccess) c->vs_armed = true;
+    }
+  } scratch_use{c, s, vs_own_meta};
   uint64_t *part = nullptr;
   PartSlot *ps = nullptr;
   if (dev_stats) {
@@ -828,6 +908,15 @@ static int launch_burst(dp_ctx_t *c, uint8_t *dev_buf, uint64_t buf_bytes, const
     hipError_t e = hipGetLastError();
     (void)dpk_mark_failed(dev_in, dev_out, dev_meta, n, s);
     return fail(DP_EIO, "kernel launch failed", e);
+  }
+  // the Stats stage, behind the last kernel that wrote the records (in the
+  // flows variant: the replay's join, dp_flow_fixup and dp_flow_apply)
+  if (c->vpc_stats) {
+    if (dpk_vpc_stats(dev_out, dev_meta, n, c->vs_tab, c->vs_blocks, s)) {
+      hipError_t e = hipGetLastError();
+      (void)dpk_mark_failed(dev_in, dev_out, dev_meta, n, s);
+      return fail(DP_EIO, "per-VPC statistics launch failed", e);
+    }
   }
   if (ps) {
     (void)hipEventRecord(ps->used, s);
@@ -1159,6 +1248,11 @@ int dp_ctx_set_option(dp_ctx_t *c, int option, int64_t value) {
     c->clock = (uint64_t)value;
     return 0;
   }
+  if (option == DP_OPT_VPC_STATS) {
+    if (value != 0 && value != 1) return fail(DP_EINVAL, "per-VPC statistics: 0 or 1");
+    c->vpc_stats = value != 0;
+    return 0;
+  }
   return fail(DP_EINVAL, "unknown option");
 }
 
@@ -1228,7 +1322,8 @@ int dp_process_burst(dp_ctx_t *c, uint8_t *buf, uint64_t buf_bytes, const dp_pkt
     c->d_buf_cap = need;
   }
   if ((e = ensure_records(c, n)) != hipSuccess) return bail(DP_ENOMEM, "burst records (device / pinned)", e);
-  dp_pkt_meta_t *dm = meta ? c->d_meta : nullptr;
+  // (with per-VPC statistics the chunks' meta records stay on the device)
+  dp_pkt_meta_t *dm = meta || c->vpc_stats ? c->d_meta : nullptr;
   hipStream_t s = c->stream;
   const uint32_t grow = [&] {
     auto img = current(c);
@@ -1502,7 +1597,7 @@ int dp_process_burst_sharded(dp_ctx_t *const *ctxs, uint32_t n_ctx, uint8_t *buf
     }
     if ((e = ensure_records(c, S.cnt)) != hipSuccess) { rc = fail(DP_ENOMEM, "hipMalloc shard records", e); break; }
     hipStream_t s = c->stream;
-    dp_pkt_meta_t *dm = meta ? c->d_meta : nullptr;
+    dp_pkt_meta_t *dm = meta || c->vpc_stats ? c->d_meta : nullptr;
     if ((e = hipMemcpyAsync(c->d_buf, buf + S.lo, bytes, hipMemcpyHostToDevice, s)) != hipSuccess ||
         (e = hipMemcpyAsync(c->d_in, S.rin.data(), sizeof(dp_pkt_in_t) * S.cnt, hipMemcpyHostToDevice, s)) != hipSuccess ||
         (stats && (e = hipMemsetAsync(c->d_stats, 0, sizeof(uint64_t) * DP_DONE_COUNT, s)) != hipSuccess)) {
@@ -1533,6 +1628,69 @@ int dp_process_burst_sharded(dp_ctx_t *const *ctxs, uint32_t n_ctx, uint8_t *buf
     if (stats && S.cnt)
       for (int r = 0; r < DP_DONE_COUNT; r++) stats[r] += S.st[r];
   }
+  return 0;
+}
+
+int dp_vpc_stats_accumulate_device(dp_ctx_t *c, const dp_pkt_out_t *dev_out, const dp_pkt_meta_t *dev_meta,
+                                   uint32_t n, void *stream) {
+  if (!c) return fail(DP_EINVAL, "null ctx");
+  if (n == 0) return 0;
+  if (!dev_out || !dev_meta) return fail(DP_EINVAL, "null records");
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  reap(c);
+  if (int rc = vs_ensure(c)) return rc;
+  if (dpk_vpc_stats(dev_out, dev_meta, n, c->vs_tab, c->vs_blocks, s))
+    return fail(DP_EIO, "per-VPC statistics launch failed", hipGetLastError());
+  // dp_vpc_stats_read waits for it like for a burst
+  InFlight f;
+  f.done = take_event(c);
+  if (f.done) (void)hipEventRecord(f.done, s);
+  c->inflight.push_back(std::move(f));
+  return 0;
+}
+
+int dp_vpc_stats_read(dp_ctx_t *c, dp_vpc_stat_t *entries, uint32_t cap, uint32_t *n_entries,
+                      uint64_t *lost_packets, int reset) {
+  if (!c || !n_entries || (cap && !entries)) return fail(DP_EINVAL, "null argument");
+  *n_entries = 0;
+  if (lost_packets) *lost_packets = 0;
+  if (!c->vs_tab) return 0;  // nothing was ever accumulated
+  (void)hipSetDevice(c->device);
+  // on the context's stream, behind every launch not yet known complete;
+  // through pinned staging, as the classifiers' copies
+  hipStream_t s = c->stream;
+  hipError_t e;
+  for (auto &f : c->inflight)
+    if (f.done && (e = hipStreamWaitEvent(s, f.done, 0)) != hipSuccess) return fail(DP_EIO, "stream wait", e);
+  if ((e = hipMemcpyAsync(c->vs_host, c->vs_tab, sizeof(dpv::Table), hipMemcpyDeviceToHost, s)) != hipSuccess ||
+      (e = hipStreamSynchronize(s)) != hipSuccess)
+    return fail(DP_EIO, "per-VPC statistics copy", e);
+  reap(c);
+  const dpv::Table &t = *c->vs_host;
+  std::vector<dp_vpc_stat_t> cells;
+  uint64_t lost = t.lost;
+  for (uint32_t h = 0; h < DP_VPC_STATS_CELLS; h++) {
+    const unsigned long long *v = t.ctr[h];
+    if (!t.key[h] || !(v[0] | v[1] | v[2] | v[3])) continue;
+    if (t.tick[h] > DP_VPC_STATS_CELLS / 2) {  // claimed past the capacity
+      lost += v[dpv::kFwdPackets] + v[dpv::kDropPackets];
+      continue;
+    }
+    cells.push_back(dp_vpc_stat_t{(uint32_t)(t.key[h] >> 32), (uint32_t)t.key[h], v[dpv::kFwdPackets],
+                                  v[dpv::kFwdBytes], v[dpv::kDropPackets], v[dpv::kDropBytes]});
+  }
+  *n_entries = (uint32_t)cells.size();
+  if (lost_packets) *lost_packets = lost;
+  if (cells.size() > cap) return fail(DP_ENOSPC, "per-VPC statistics: more cells than the array holds");
+  std::sort(cells.begin(), cells.end(), [](const dp_vpc_stat_t &a, const dp_vpc_stat_t &b) {
+    return a.src_vni != b.src_vni ? a.src_vni < b.src_vni : a.dst_vni < b.dst_vni;
+  });
+  if (!cells.empty()) std::memcpy(entries, cells.data(), sizeof(dp_vpc_stat_t) * cells.size());
+  // the clear follows the copy on the same stream and the call returns after
+  // it: no launch of this context falls between the two
+  if (reset && ((e = hipMemsetAsync(c->vs_tab, 0, sizeof(dpv::Table), s)) != hipSuccess ||
+                (e = hipStreamSynchronize(s)) != hipSuccess))
+    return fail(DP_EIO, "per-VPC statistics reset", e);
   return 0;
 }
 

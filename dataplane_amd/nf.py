@@ -252,6 +252,29 @@ class GpuPathNf:
                                               out.ctypes.data), "dp_ff_classify_match", self.lib)
         return out
 
+    # -- per-VPC statistics (the Stats stage, stats/src/dpstats.rs:914-1011) ----
+    def set_vpc_stats(self, on: bool) -> None:
+        """dp_ctx_set_option(DP_OPT_VPC_STATS): every burst that follows is
+        accounted into the context's per-VPC statistics on the device."""
+        self.set_option(A.OPT_VPC_STATS, 1 if on else 0)
+
+    def vpc_stats_accumulate_device(self, dev_out: int, dev_meta: int, n: int,
+                                    stream: Optional[int] = None) -> None:
+        """The stage alone over n device-resident dp_pkt_out_t / dp_pkt_meta_t
+        records (dp_vpc_stats_accumulate_device): raw device pointers."""
+        A.check(self.lib.dp_vpc_stats_accumulate_device(self.ctx, dev_out, dev_meta, n, stream),
+                "dp_vpc_stats_accumulate_device", self.lib)
+
+    def vpc_stats(self, reset: bool = False):
+        """(A.VPC_STAT records sorted by (src_vni, dst_vni), lost packets) of
+        dp_vpc_stats_read; `reset` clears the counters with the read."""
+        cells = np.zeros(A.VPC_STATS_CELLS // 2, dtype=A.VPC_STAT)
+        n, lost = C.c_uint32(0), C.c_uint64(0)
+        A.check(self.lib.dp_vpc_stats_read(self.ctx, cells.ctypes.data, len(cells), C.byref(n),
+                                           C.byref(lost), 1 if reset else 0),
+                "dp_vpc_stats_read", self.lib)
+        return cells[:n.value].copy(), int(lost.value)
+
     def close(self) -> None:
         if self.ctx:
             self.lib.dp_ctx_destroy(self.ctx)

@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define DPGPU_ABI_VERSION 7u
+#define DPGPU_ABI_VERSION 8u
 
 /* Bytes every frame must have in front of it (its own scratch, owned by the
  * packet).  Output headers are written in place into this headroom: VXLAN
@@ -165,7 +165,9 @@ enum dp_pm_flag {
 
 /* The rest of PacketMeta (net/src/packet/meta.rs:138-154), 48 B, written
  * only when the caller passes a meta array: the fields a CPU stage kept
- * after the GPU block (PacketStatsNF, per-VPC stats, a dumper) would read. */
+ * after the GPU block (PacketStatsNF, a dumper) would read.  The per-VPC
+ * Stats stage reads src_vni / dst_vni on the device (DP_OPT_VPC_STATS below)
+ * and needs no meta array on the host. */
 typedef struct dp_pkt_meta {
     uint32_t dst_vni;    /* PacketMeta.dst_vpcd VNI (0 if None) */
     uint32_t src_vni;    /* PacketMeta.src_vpcd VNI (0 if None) */
@@ -507,6 +509,7 @@ typedef struct dp_tables_desc {
 #define DP_ENOTSUP (-95)   /* a table form the path does not support */
 #define DP_EIO (-5)        /* HIP runtime failure */
 #define DP_ENOTABLES (-61) /* no tables published yet (ENODATA) */
+#define DP_ENOSPC (-28)    /* the caller's array is too small */
 
 /* ------------------------------------------------------------------------ */
 /* Entry points.                                                             */
@@ -617,7 +620,19 @@ enum dp_ctx_option {
      * bursts that follow.  PortForwarder sets the expiry of the flows it
      * creates or refreshes to now + the rule's timeout
      * (flow_state.rs:233-263, flow_info.rs:399-407). */
-    DP_OPT_CLOCK = 2
+    DP_OPT_CLOCK = 2,
+    /* 1: every burst of the context (dp_process_burst, _device, _sharded,
+     * dp_process_mbufs) is accounted into the context's per-VPC statistics
+     * ("Per-VPC statistics" below) on the burst's stream, after the last
+     * kernel that writes its records.  A burst without a meta array writes
+     * its meta records into a context-owned device scratch array instead
+     * (nothing more goes to the host); such bursts of one context on
+     * different streams run one after the other.  A burst that fails whole
+     * records nothing.  Where the records are pinned host memory (the
+     * zero-copy host path, dp_process_mbufs) the stage reads them back over
+     * PCIe: 16 B a packet, 24 B with a caller's meta array.
+     * 0 (default): no launch, no allocation. */
+    DP_OPT_VPC_STATS = 3
 };
 enum dp_host_path { DP_HOST_AUTO = 0, DP_HOST_COPY = 1, DP_HOST_ZERO_COPY = 2 };
 int dp_ctx_set_option(dp_ctx_t *ctx, int option, int64_t value);
@@ -945,6 +960,56 @@ int dp_process_mbufs(dp_ctx_t *ctx, const void *pool_base, uint64_t pool_bytes,
                      void *const *mbufs, uint32_t n, const dp_mbuf_layout_t *layout,
                      const uint32_t *port_ifindex, uint32_t n_ports, dp_pkt_out_t *out,
                      dp_pkt_meta_t *meta, uint64_t *stats);
+
+/* ------------------------------------------------------------------------ */
+/* Per-VPC statistics: the reference's Stats stage (stats/src/dpstats.rs:     */
+/* 914-1011, Stats::process :942-1007), the accounting stage after Egress,    */
+/* on the device.  Per packet i of a burst, from the records the path wrote:  */
+/*   src = meta[i].src_vni, dst = meta[i].dst_vni (0: None),                  */
+/*   bytes = out[i].len, drop = out[i].done != DP_DONE_DELIVERED              */
+/*   (DP_DONE_NONE and Local count as drops, as the reference counts them);   */
+/*   src == 0: nothing; drop: the drop total of src gains (1, bytes) and, if  */
+/*   dst != 0, the pair-drop cell (src, dst) too; delivered with dst != 0:    */
+/*   the forward cell (src, dst) gains (1, bytes); delivered, dst == 0:       */
+/*   nothing.                                                                 */
+/* Counters are u64, per context, cumulative across bursts until read with    */
+/* reset, and independent of table generations (a publish leaves them).       */
+/* Boundary: a delivered packet's out.len is its serialized length (the       */
+/* reference's total_len() at the Stats stage); a dropped packet's out.len is */
+/* the frame as received (in.len), where the reference counts total_len() at  */
+/* the point of the drop (different after a decap or an encap): drop bytes    */
+/* are "bytes received".  The reference never rate-smooths drop bytes.        */
+/* ------------------------------------------------------------------------ */
+typedef struct dp_vpc_stat {
+    uint32_t src_vni, dst_vni;  /* dst_vni == 0: src_vni's drop total (fwd_* are 0) */
+    uint64_t fwd_packets, fwd_bytes;
+    uint64_t drop_packets, drop_bytes;
+} dp_vpc_stat_t;                /* 40 B */
+
+/* Slots of the context's device table of cells (open addressing).  At most
+ * half of them hold reported cells: the first DP_VPC_STATS_CELLS / 2 distinct
+ * cells since the last reset, in claim order.  Every update of a later cell
+ * counts its packets into `lost_packets` instead, so a reported cell is
+ * always exact. */
+#define DP_VPC_STATS_CELLS 4096u
+
+/* The stage alone over n device-resident records (stream as in
+ * dp_process_burst_device; asynchronous there), whatever DP_OPT_VPC_STATS is. */
+int dp_vpc_stats_accumulate_device(dp_ctx_t *ctx, const dp_pkt_out_t *dev_out,
+                                   const dp_pkt_meta_t *dev_meta, uint32_t n, void *stream);
+/* Read the cells, sorted by (src_vni, dst_vni), all-zero cells omitted.
+ * A call of the context's own thread, like every other (Conventions above):
+ * the worker reads on its tick and hands the cells to whoever collects them.
+ * Synchronous, ordered after every burst and accumulate call the context has
+ * launched (the caller synchronises streams it owns, as for dev_out).
+ * `*n_entries` receives the number of cells; with cap too small nothing is
+ * copied or reset and the call returns DP_ENOSPC.  `lost_packets` (may be
+ * NULL) receives the packets of cells that found no slot.  `reset` != 0
+ * clears every counter and lost_packets with the read: the table is copied
+ * and then cleared on the context's stream, behind every burst launched so
+ * far and before the call returns, so no update falls between the two. */
+int dp_vpc_stats_read(dp_ctx_t *ctx, dp_vpc_stat_t *entries, uint32_t cap, uint32_t *n_entries,
+                      uint64_t *lost_packets, int reset);
 
 /* Introspection: bytes of the device table image and its parts (for
  * DESIGN.md / bench), and the last HIP error string. */

@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_DIR = os.path.join(HERE, "lib")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 HEADROOM = 96
 
 # DoneReason (net/src/packet/meta.rs:84-119)
@@ -266,7 +266,8 @@ GPU_SYMBOLS = ["dp_abi_version", "dp_ctx_create", "dp_ctx_destroy", "dp_tables_p
                "dp_process_mbufs", "dp_acl_classify", "dp_acl_classify_device",
                "dp_acl_key_from_match", "dp_acl_classify_match", "dp_ff_classify",
                "dp_ff_classify_device", "dp_ff_key_from_match", "dp_ff_classify_match",
-               "dp_vpc_stats_accumulate_device", "dp_vpc_stats_read"]
+               "dp_vpc_stats_accumulate_device", "dp_vpc_stats_read", "dp_fib_lookup",
+               "dp_fib_lookup_device"]
 # dp_acl_key_t / dp_acl_result_t (the ACL classifier alone)
 ACL_KEY = np.dtype([("src_vni", "<u4"), ("dst_vni", "<u4"), ("family", "u1"), ("proto", "u1"),
                     ("sport", "<u2"), ("dport", "<u2"), ("pad", "u1", 2), ("src", "u1", 16),
@@ -291,9 +292,17 @@ VPC_STAT = np.dtype([("src_vni", "<u4"), ("dst_vni", "<u4"), ("fwd_packets", "<u
                      ("drop_packets", "<u8"), ("drop_bytes", "<u8")])
 VPC_STATS_CELLS = 4096  # DP_VPC_STATS_CELLS
 ENOSPC = -28
+# dp_fib_key_t / dp_fib_result_t (the FIB lookup alone: FibReader::lpm_route,
+# routing/src/fib/fibtype.rs:440-443)
+FIB_KEY = np.dtype([("vrf_id", "<u4"), ("family", "u1"), ("pad", "u1", 3), ("addr", "u1", 16)])
+FIB_RESULT = np.dtype([("nh", "<u4"), ("n_entries", "<u2"), ("code", "u1"), ("pad", "u1")])
+assert FIB_KEY.itemsize == 24 and FIB_RESULT.itemsize == 8
+FIB_ROUTE, FIB_DEFAULT, FIB_NO_VRF, FIB_BAD_FAMILY = 0, 1, 2, 3
+FIB_NO_NH = 0xFFFFFFFF
+ENOTABLES = -61  # DP_ENOTABLES
 NP_STRUCTS = dict(dp_flow_key_t=FLOW_KEY, dp_flow_t=FLOW, dp_flow_info_t=FLOW_INFO, dp_acl_key_t=ACL_KEY,
                   dp_acl_result_t=ACL_RESULT, dp_ff_input_t=FF_INPUT, dp_ff_result_t=FF_RESULT,
-                  dp_vpc_stat_t=VPC_STAT)
+                  dp_vpc_stat_t=VPC_STAT, dp_fib_key_t=FIB_KEY, dp_fib_result_t=FIB_RESULT)
 
 
 class MbufLayout(C.Structure):
@@ -404,6 +413,9 @@ def gpu_lib() -> C.CDLL:
         lib.dp_vpc_stats_accumulate_device.argtypes = [_VP, _VP, _VP, C.c_uint32, _VP]
         lib.dp_vpc_stats_read.argtypes = [_VP, _VP, C.c_uint32, C.POINTER(C.c_uint32),
                                           C.POINTER(C.c_uint64), C.c_int]
+        lib.dp_fib_lookup.argtypes = [_VP, _VP, _VP, C.c_uint32]
+        lib.dp_fib_lookup_device.argtypes = [_VP, _VP, _VP, C.c_uint32, _VP]
+        lib.dpd_debug_set_fib_lookup_form.argtypes = [C.c_int]
         lib.dpd_debug_classify_copies.argtypes = [C.c_int]
         lib.dpd_debug_hip_runtimes.restype = C.c_int
         lib.dpf_debug_nat_sequential.argtypes = [C.c_int]

@@ -47,6 +47,8 @@ extern "C" int dpk_acl_classify(const uint8_t *img_base, const void *image_dev, 
                                 dp_acl_result_t *out, uint32_t n, hipStream_t stream);
 extern "C" int dpk_ff_classify(const uint8_t *img_base, const void *image_dev, const dp_ff_input_t *in,
                                dp_ff_result_t *out, uint32_t n, int stage, hipStream_t stream);
+extern "C" int dpk_fib_lookup(const uint8_t *img_base, const void *image_dev, const dp_fib_key_t *keys,
+                              dp_fib_result_t *out, uint32_t n, hipStream_t stream);
 extern "C" int dpk_mark_failed(const dp_pkt_in_t *in, dp_pkt_out_t *out, dp_pkt_meta_t *meta, uint32_t n,
                                hipStream_t stream);
 extern "C" int dpk_stage_expand(const uint8_t *cin, const uint32_t *pos, const dp_pkt_in_t *in, uint8_t *buf,
@@ -1134,6 +1136,39 @@ int dp_ff_classify_match(dp_ctx_t *c, int table, const uint8_t *match, uint32_t 
   const int rc = dp_ff_key_from_match(table, match, key_size, stride, n, in.data());
   if (rc || !n) return rc;
   return ff_classify_host(c, in.data(), out, n, table);
+}
+
+// The FIB lookup alone (dp_fiblookup.hip); the image is captured and retired
+// as dp_acl_classify_device does it.
+int dp_fib_lookup_device(dp_ctx_t *c, const dp_fib_key_t *dev_keys, dp_fib_result_t *dev_out, uint32_t n,
+                         void *stream) {
+  if (!c) return fail(DP_EINVAL, "null ctx");
+  if (n == 0) return 0;
+  if (!dev_keys || !dev_out) return fail(DP_EINVAL, "null keys / results");
+  if (((uintptr_t)dev_keys | (uintptr_t)dev_out) & 7) return fail(DP_EINVAL, "FIB keys / results not 8-byte aligned");
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  reap(c);
+  auto img = current(c);
+  if (!img) return fail(DP_ENOTABLES, "no tables published");
+  if (dpk_fib_lookup(img->dev, img->dev + img->im_off, dev_keys, dev_out, n, s))
+    return fail(DP_EIO, "FIB lookup launch failed", hipGetLastError());
+  InFlight f;
+  f.img = img;
+  f.done = take_event(c);
+  if (f.done) (void)hipEventRecord(f.done, s);
+  c->inflight.push_back(std::move(f));
+  return 0;
+}
+
+int dp_fib_lookup(dp_ctx_t *c, const dp_fib_key_t *keys, dp_fib_result_t *out, uint32_t n) {
+  if (!c) return fail(DP_EINVAL, "null ctx");
+  if (n == 0) return 0;
+  if (!keys || !out) return fail(DP_EINVAL, "null keys / results");
+  return classify_host(c, keys, sizeof(dp_fib_key_t) * (size_t)n, out, sizeof(dp_fib_result_t) * (size_t)n,
+                       [&](const void *dk, void *dr) {
+                         return dp_fib_lookup_device(c, static_cast<const dp_fib_key_t *>(dk),
+                                                     static_cast<dp_fib_result_t *>(dr), n, c->stream);
+                       });
 }
 
 int dp_ctx_attach_flow_table(dp_ctx_t *c, dp_flow_table_t *ft) {

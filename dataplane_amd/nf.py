@@ -252,6 +252,22 @@ class GpuPathNf:
                                               out.ctypes.data), "dp_ff_classify_match", self.lib)
         return out
 
+    def fib_lookup(self, keys: np.ndarray) -> np.ndarray:
+        """The FIB lookup alone (dp_fib_lookup): A.FIB_KEY records -> A.FIB_RESULT
+        records in input order -- FibReader::lpm_route per key
+        (routing/src/fib/fibtype.rs:440-443)."""
+        keys = np.ascontiguousarray(np.atleast_1d(keys), dtype=A.FIB_KEY)
+        out = np.zeros(len(keys), dtype=A.FIB_RESULT)
+        A.check(self.lib.dp_fib_lookup(self.ctx, keys.ctypes.data, out.ctypes.data, len(keys)),
+                "dp_fib_lookup", self.lib)
+        return out
+
+    def fib_lookup_device(self, dev_keys: int, dev_out: int, n: int, stream: Optional[int] = None) -> None:
+        """n device-resident keys (dp_fib_lookup_device): raw device pointers,
+        asynchronous on `stream`."""
+        A.check(self.lib.dp_fib_lookup_device(self.ctx, dev_keys, dev_out, n, stream),
+                "dp_fib_lookup_device", self.lib)
+
     # -- per-VPC statistics (the Stats stage, stats/src/dpstats.rs:914-1011) ----
     def set_vpc_stats(self, on: bool) -> None:
         """dp_ctx_set_option(DP_OPT_VPC_STATS): every burst that follows is

@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define DPGPU_ABI_VERSION 8u
+#define DPGPU_ABI_VERSION 9u
 
 /* Bytes every frame must have in front of it (its own scratch, owned by the
  * packet).  Output headers are written in place into this headroom: VXLAN
@@ -760,6 +760,50 @@ int dp_ff_key_from_match(int table, const uint8_t *match, uint32_t key_size, uin
                          dp_ff_input_t *out);
 int dp_ff_classify_match(dp_ctx_t *ctx, int table, const uint8_t *match, uint32_t key_size,
                          uint32_t stride, uint32_t n, dp_ff_result_t *out);
+
+/* ------------------------------------------------------------------------ */
+/* The FIB lookup alone: the longest prefix match behind IP-Forward as a     */
+/* batch lookup -- FibReader::lpm_route / Fib::lpm (routing/src/fib/         */
+/* fibtype.rs:239-257, 440-443) over the published routes.  Per key, the FIB */
+/* of the key's VRF (FibKey::Id, dp_fib_t.vrf_id) is searched for the        */
+/* longest published route covering the address; the result names that       */
+/* route's dp_route_nh_t.  A FIB always answers: where no published route    */
+/* covers the key, the answer is the FIB's implicit drop default             */
+/* (DP_FIB_DEFAULT), never an index; a /0 the caller published is a route    */
+/* like any other.  Keys are never reordered: out[i] answers keys[i].        */
+/* Declared boundaries: the matched prefix itself (lpm_with_prefix) is not   */
+/* reported -- the device tables' leaves hold the next hop alone --, and no  */
+/* ECMP entry is chosen (that needs the packet's hash): n_entries says how   */
+/* many there are.                                                           */
+/* ------------------------------------------------------------------------ */
+typedef struct dp_fib_key {
+    uint32_t vrf_id;     /* FibKey::Id of the FIB to search (dp_fib_t.vrf_id) */
+    uint8_t  family;     /* 4 or 6 */
+    uint8_t  pad[3];
+    uint8_t  addr[16];   /* network byte order; v4 in the first 4 bytes */
+} dp_fib_key_t;          /* 24 B */
+
+enum dp_fib_code {
+    DP_FIB_ROUTE = 0,       /* a published route covers the key */
+    DP_FIB_DEFAULT = 1,     /* none does: the FIB's implicit drop default */
+    DP_FIB_NO_VRF = 2,      /* no published FIB has the key's vrf_id */
+    DP_FIB_BAD_FAMILY = 3   /* a family other than 4 / 6 (whatever the vrf_id) */
+};
+typedef struct dp_fib_result {
+    uint32_t nh;         /* index into the published route_nhs[] of the longest matching
+                            route; UINT32_MAX when code != DP_FIB_ROUTE */
+    uint16_t n_entries;  /* that dp_route_nh_t's n_entries (> 1: ECMP), else 0 */
+    uint8_t  code;       /* enum dp_fib_code */
+    uint8_t  pad;
+} dp_fib_result_t;       /* 8 B */
+
+/* n keys resident on the context's device into dev_out, both 8-byte aligned
+ * (DP_EINVAL otherwise; stream as in dp_process_burst_device; asynchronous
+ * there).  DP_ENOTABLES before a publish; n = 0 is DP_OK and launches nothing. */
+int dp_fib_lookup_device(dp_ctx_t *ctx, const dp_fib_key_t *dev_keys, dp_fib_result_t *dev_out,
+                         uint32_t n, void *stream);
+/* The same for keys and results in host memory (synchronous; any alignment). */
+int dp_fib_lookup(dp_ctx_t *ctx, const dp_fib_key_t *keys, dp_fib_result_t *out, uint32_t n);
 
 /* ------------------------------------------------------------------------ */
 /* Flow table: FlowTable                              */

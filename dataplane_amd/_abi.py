@@ -267,7 +267,8 @@ GPU_SYMBOLS = ["dp_abi_version", "dp_ctx_create", "dp_ctx_destroy", "dp_tables_p
                "dp_acl_key_from_match", "dp_acl_classify_match", "dp_ff_classify",
                "dp_ff_classify_device", "dp_ff_key_from_match", "dp_ff_classify_match",
                "dp_vpc_stats_accumulate_device", "dp_vpc_stats_read", "dp_fib_lookup",
-               "dp_fib_lookup_device"]
+               "dp_fib_lookup_device", "dp_capture_open", "dp_capture_set_filter",
+               "dp_capture_close", "dp_capture_device", "dp_capture_read"]
 # dp_acl_key_t / dp_acl_result_t (the ACL classifier alone)
 ACL_KEY = np.dtype([("src_vni", "<u4"), ("dst_vni", "<u4"), ("family", "u1"), ("proto", "u1"),
                     ("sport", "<u2"), ("dport", "<u2"), ("pad", "u1", 2), ("src", "u1", 16),
@@ -300,9 +301,25 @@ assert FIB_KEY.itemsize == 24 and FIB_RESULT.itemsize == 8
 FIB_ROUTE, FIB_DEFAULT, FIB_NO_VRF, FIB_BAD_FAMILY = 0, 1, 2, 3
 FIB_NO_NH = 0xFFFFFFFF
 ENOTABLES = -61  # DP_ENOTABLES
+EINVAL = -22  # DP_EINVAL
+# packet capture (include/dpgpu.h "Packet capture": the reference's PacketDumper,
+# pipeline/src/sample_nfs.rs:41-150): dp_capture_filter_t / dp_cap_rec_t
+_PREFIX = [("family", "u1"), ("len", "u1"), ("pad", "u1", 2), ("addr", "u1", 16)]
+CAP_FILTER = np.dtype([("clauses", "<u4"), ("l4_mask", "<u4"), ("done_mask", "<u8"), ("src_vni", "<u4"),
+                       ("dst_vni", "<u4"), ("src", _PREFIX), ("dst", _PREFIX), ("sport_lo", "<u2"),
+                       ("sport_hi", "<u2"), ("dport_lo", "<u2"), ("dport_hi", "<u2"), ("snaplen", "<u4"),
+                       ("pad", "<u4")])
+CAP_REC = np.dtype([("off", "<u8"), ("burst", "<u4"), ("index", "<u4"), ("len", "<u2"), ("caplen", "<u2"),
+                    ("tap", "u1"), ("done", "u1"), ("pad", "<u2"), ("src_vni", "<u4"), ("dst_vni", "<u4")])
+assert CAP_FILTER.itemsize == 80 and CAP_REC.itemsize == 32
+CAP_RX, CAP_TX = 1, 2                                                    # enum dp_cap_tap
+CAPC_UDP, CAPC_TCP, CAPC_ICMP4, CAPC_ICMP6, CAPC_VXLAN = 1, 2, 4, 8, 16  # enum dp_cap_class
+(CAPF_L4, CAPF_SRC, CAPF_DST, CAPF_SPORT, CAPF_DPORT, CAPF_DONE, CAPF_SRC_VNI,
+ CAPF_DST_VNI) = (1 << i for i in range(8))                              # enum dp_capf
 NP_STRUCTS = dict(dp_flow_key_t=FLOW_KEY, dp_flow_t=FLOW, dp_flow_info_t=FLOW_INFO, dp_acl_key_t=ACL_KEY,
                   dp_acl_result_t=ACL_RESULT, dp_ff_input_t=FF_INPUT, dp_ff_result_t=FF_RESULT,
-                  dp_vpc_stat_t=VPC_STAT, dp_fib_key_t=FIB_KEY, dp_fib_result_t=FIB_RESULT)
+                  dp_vpc_stat_t=VPC_STAT, dp_fib_key_t=FIB_KEY, dp_fib_result_t=FIB_RESULT,
+                  dp_capture_filter_t=CAP_FILTER, dp_cap_rec_t=CAP_REC)
 
 
 class MbufLayout(C.Structure):
@@ -318,6 +335,7 @@ MBUF_LAYOUT_DPDK = MbufLayout(0, 16, 20, 22, 36, 40, 54, 0)  # DP_MBUF_LAYOUT_DP
 OPT_HOST_PATH = 1
 OPT_CLOCK = 2
 OPT_VPC_STATS = 3
+OPT_CAPTURE = 4
 HOST_AUTO, HOST_COPY, HOST_ZERO_COPY = 0, 1, 2
 
 _VP = C.c_void_p
@@ -415,6 +433,13 @@ def gpu_lib() -> C.CDLL:
                                           C.POINTER(C.c_uint64), C.c_int]
         lib.dp_fib_lookup.argtypes = [_VP, _VP, _VP, C.c_uint32]
         lib.dp_fib_lookup_device.argtypes = [_VP, _VP, _VP, C.c_uint32, _VP]
+        lib.dp_capture_open.argtypes = [_VP, _VP, C.c_uint32, C.c_uint64]
+        lib.dp_capture_set_filter.argtypes = [_VP, _VP]
+        lib.dp_capture_close.argtypes = [_VP]
+        lib.dp_capture_device.argtypes = [_VP, C.c_int, _VP, C.c_uint64, _VP, _VP, C.c_uint32, _VP]
+        lib.dp_capture_read.argtypes = [_VP, _VP, C.c_uint32, _VP, C.c_uint64, C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                        C.POINTER(C.c_uint64), C.c_int]
         lib.dpd_debug_set_fib_lookup_form.argtypes = [C.c_int]
         lib.dpd_debug_classify_copies.argtypes = [C.c_int]
         lib.dpd_debug_hip_runtimes.restype = C.c_int

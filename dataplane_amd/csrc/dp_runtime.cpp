@@ -36,7 +36,13 @@
 #include "dp_flows_rt.h"
 #include "dp_tables.h"
 #include "dp_vpcstats.h"
+#include "dp_capture.h"
 
+extern "C" int dpk_capture(int tap, const uint8_t *buf, uint64_t buf_bytes, const void *recs,
+                           const dp_pkt_meta_t *meta, uint32_t n, const dpc::Filter *f, void *scratch,
+                           void *state, void *out_recs, void *out_bytes, uint32_t max_records,
+                           uint64_t max_units, hipStream_t stream);
+extern "C" int dpk_capture_reset(void *state, hipStream_t stream);
 extern "C" int dpk_vpc_stats(const dp_pkt_out_t *out, const dp_pkt_meta_t *meta, uint32_t n, void *table,
                              uint32_t max_blocks, hipStream_t stream);
 extern "C" int dpk_launch_pipeline(const uint8_t *img_base, const void *image_dev, uint8_t *buf,
@@ -299,6 +305,22 @@ struct dp_ctx {
   uint32_t vs_meta_cap = 0;
   hipEvent_t vs_used = nullptr;
   bool vs_armed = false;
+  // packet capture (dp_capture_open .. dp_capture_close): the taps the bursts
+  // run (DP_OPT_CAPTURE), the filter, the device buffer (counters, records,
+  // bytes), the launch scratch (select words and tile records, grown on
+  // demand) and the event that orders one capture launch behind the last
+  bool cp_open = false;
+  int cp_taps = 0;
+  dpc::Filter cp_filter{};
+  dpc::State *cp_state = nullptr, *cp_host = nullptr;
+  dp_cap_rec_t *cp_recs = nullptr;
+  uint8_t *cp_bytes = nullptr;
+  uint32_t cp_max_recs = 0;
+  uint64_t cp_max_units = 0;
+  void *cp_scratch = nullptr;
+  uint64_t cp_scratch_cap = 0;
+  hipEvent_t cp_used = nullptr;
+  bool cp_armed = false;
   // host threads of the staged-copy path, the context's own: a staged burst
   // waits for its own chunks only, never for another worker's
   std::unique_ptr<HostPool> pool;
@@ -514,6 +536,80 @@ int vs_ensure(dp_ctx *c) {
   return 0;
 }
 
+// dp_capture_filter_t -> the select kernel's form; DP_EINVAL for a clause
+// that cannot be evaluated.
+int cp_lower(const dp_capture_filter_t *in, dpc::Filter *out) {
+  dpc::Filter f{};
+  if (in) {
+    const uint32_t all = DP_CAPF_L4 | DP_CAPF_SRC | DP_CAPF_DST | DP_CAPF_SPORT | DP_CAPF_DPORT | DP_CAPF_DONE |
+                         DP_CAPF_SRC_VNI | DP_CAPF_DST_VNI;
+    if (in->clauses & ~all) return fail(DP_EINVAL, "capture filter: unknown clause");
+    f.clauses = in->clauses;
+    f.l4_mask = in->l4_mask;
+    f.done_mask = in->done_mask;
+    f.src_vni = in->src_vni;
+    f.dst_vni = in->dst_vni;
+    f.sport_lo = in->sport_lo, f.sport_hi = in->sport_hi, f.dport_lo = in->dport_lo, f.dport_hi = in->dport_hi;
+    f.snaplen = in->snaplen;
+    struct P { uint32_t clause; const dp_prefix_t *p; uint32_t *fam, *addr, *mask; };
+    for (const P &x : {P{DP_CAPF_SRC, &in->src, &f.src_fam, f.src, f.src_mask},
+                       P{DP_CAPF_DST, &in->dst, &f.dst_fam, f.dst, f.dst_mask}}) {
+      if (!(in->clauses & x.clause)) continue;
+      const uint32_t bits = x.p->family == 4 ? 32u : 128u;
+      if ((x.p->family != 4 && x.p->family != 6) || x.p->len > bits)
+        return fail(DP_EINVAL, "capture filter: bad prefix");
+      uint8_t m[16] = {};
+      for (uint32_t b = 0; b < x.p->len; b++) m[b >> 3] |= (uint8_t)(0x80u >> (b & 7));
+      *x.fam = x.p->family;
+      std::memcpy(x.addr, x.p->addr, 16);  // words in memory order, as the kernel reads the frame
+      std::memcpy(x.mask, m, 16);
+    }
+  }
+  *out = f;
+  return 0;
+}
+
+// One capture launch (the three kernels of dp_capture.hip) over n records on
+// `s`, ordered behind the context's previous one: they share the scratch and
+// append to one buffer.
+int cp_launch(dp_ctx *c, int tap, const uint8_t *dev_buf, uint64_t buf_bytes, const void *dev_recs,
+              const dp_pkt_meta_t *dev_meta, uint32_t n, hipStream_t s) {
+  if (tap != DP_CAP_RX && tap != DP_CAP_TX) return fail(DP_EINVAL, "capture: bad tap");
+  if (!c->cp_open) return fail(DP_EINVAL, "capture: none open");
+  if (n == 0) return 0;
+  if (!dev_buf || ((uintptr_t)dev_buf & 15) || !dev_recs || ((uintptr_t)dev_recs & 15) || ((uintptr_t)dev_meta & 7))
+    return fail(DP_EINVAL, "capture: null or misaligned burst");
+  const uint32_t cl = c->cp_filter.clauses, vni = DP_CAPF_SRC_VNI | DP_CAPF_DST_VNI;
+  if (tap == DP_CAP_RX && (cl & (DP_CAPF_DONE | vni))) return fail(DP_EINVAL, "capture: DONE / VNI clause on the RX tap");
+  if ((cl & vni) && !dev_meta) return fail(DP_EINVAL, "capture: VNI clause without a meta array");
+  const uint64_t need = dpc::scratch_bytes(n);
+  if (need > c->cp_scratch_cap) {
+    if (c->cp_armed) (void)hipEventSynchronize(c->cp_used);
+    if (c->cp_scratch) (void)hipFree(c->cp_scratch);
+    c->cp_scratch = nullptr;
+    c->cp_scratch_cap = 0;
+    if (hipMalloc(&c->cp_scratch, need) != hipSuccess) return fail(DP_ENOMEM, "capture scratch");
+    c->cp_scratch_cap = need;
+  }
+  if (c->cp_armed && hipStreamWaitEvent(s, c->cp_used, 0) != hipSuccess) return fail(DP_EIO, "stream wait");
+  const int rc = dpk_capture(tap, dev_buf, buf_bytes, dev_recs, dev_meta, n, &c->cp_filter, c->cp_scratch, c->cp_state,
+                             c->cp_recs, c->cp_bytes, c->cp_max_recs, c->cp_max_units, s);
+  // (whatever was enqueued uses the scratch, also on a failure)
+  if (hipEventRecord(c->cp_used, s) == hipSuccess) c->cp_armed = true;
+  return rc ? fail(DP_EIO, "capture launch failed", hipGetLastError()) : 0;
+}
+
+void cp_free(dp_ctx *c) {
+  if (c->cp_used) { (void)hipEventSynchronize(c->cp_used); (void)hipEventDestroy(c->cp_used); }
+  if (c->cp_state) (void)hipFree(c->cp_state);
+  if (c->cp_host) (void)hipHostFree(c->cp_host);
+  if (c->cp_recs) (void)hipFree(c->cp_recs);
+  if (c->cp_bytes) (void)hipFree(c->cp_bytes);
+  if (c->cp_scratch) (void)hipFree(c->cp_scratch);
+  c->cp_used = nullptr, c->cp_state = c->cp_host = nullptr, c->cp_recs = nullptr, c->cp_bytes = nullptr;
+  c->cp_scratch = nullptr, c->cp_scratch_cap = 0, c->cp_armed = false, c->cp_open = false;
+}
+
 // The meta scratch of a statistics burst without a meta array, for n packets,
 // ordered on `s` behind the burst that used it last.
 dp_pkt_meta_t *vs_scratch(dp_ctx *c, uint32_t n, hipStream_t s) {
@@ -622,6 +718,7 @@ int dp_ctx_destroy(dp_ctx_t *c) {
   if (c->vs_tab) (void)hipFree(c->vs_tab);
   if (c->vs_host) (void)hipHostFree(c->vs_host);
   if (c->vs_meta) (void)hipFree(c->vs_meta);
+  cp_free(c);
   if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
   if (c->side_fork) (void)hipEventDestroy(c->side_fork);
   if (c->side_fork2) (void)hipEventDestroy(c->side_fork2);
@@ -726,7 +823,11 @@ static int launch_burst(dp_ctx_t *c, uint8_t *dev_buf, uint64_t buf_bytes, const
   // per-VPC statistics: the stage reads the burst's meta records, the
   // context's scratch where the caller passes no array
   bool vs_own_meta = false;
-  if (c->vpc_stats) {
+  // packet capture: the taps this burst runs; a TX tap with a VNI clause
+  // reads meta records too (the same scratch where the caller passes none)
+  const int cp_taps = c->cp_open ? c->cp_taps : 0;
+  const bool cp_meta = (cp_taps & DP_CAP_TX) && (c->cp_filter.clauses & (DP_CAPF_SRC_VNI | DP_CAPF_DST_VNI));
+  if (c->vpc_stats || (cp_meta && !dev_meta)) {
     int vrc = vs_ensure(c);
     if (!vrc && !dev_meta) {
       vs_own_meta = true;
@@ -748,6 +849,13 @@ static int launch_burst(dp_ctx_t *c, uint8_t *dev_buf, uint64_t buf_bytes, const
       if (on && hipEventRecord(c->vs_used, s) == hipSuccess) c->vs_armed = true;
     }
   } scratch_use{c, s, vs_own_meta};
+  // the RX tap: the frames as received, before any kernel of the path
+  if (cp_taps & DP_CAP_RX) {
+    if (int crc = cp_launch(c, DP_CAP_RX, dev_buf, buf_bytes, dev_in, nullptr, n, s)) {
+      (void)dpk_mark_failed(dev_in, dev_out, dev_meta, n, s);
+      return crc;
+    }
+  }
   uint64_t *part = nullptr;
   PartSlot *ps = nullptr;
   if (dev_stats) {
@@ -918,6 +1026,13 @@ static int launch_burst(dp_ctx_t *c, uint8_t *dev_buf, uint64_t buf_bytes, const
       hipError_t e = hipGetLastError();
       (void)dpk_mark_failed(dev_in, dev_out, dev_meta, n, s);
       return fail(DP_EIO, "per-VPC statistics launch failed", e);
+    }
+  }
+  // the TX tap, behind the Stats stage: the records and frames as they leave
+  if (cp_taps & DP_CAP_TX) {
+    if (int crc = cp_launch(c, DP_CAP_TX, dev_buf, buf_bytes, dev_out, dev_meta, n, s)) {
+      (void)dpk_mark_failed(dev_in, dev_out, dev_meta, n, s);
+      return crc;
     }
   }
   if (ps) {
@@ -1286,6 +1401,11 @@ int dp_ctx_set_option(dp_ctx_t *c, int option, int64_t value) {
   if (option == DP_OPT_VPC_STATS) {
     if (value != 0 && value != 1) return fail(DP_EINVAL, "per-VPC statistics: 0 or 1");
     c->vpc_stats = value != 0;
+    return 0;
+  }
+  if (option == DP_OPT_CAPTURE) {
+    if (value & ~(int64_t)(DP_CAP_RX | DP_CAP_TX)) return fail(DP_EINVAL, "capture: a mask of DP_CAP_RX / DP_CAP_TX");
+    c->cp_taps = (int)value;
     return 0;
   }
   return fail(DP_EINVAL, "unknown option");
@@ -1726,6 +1846,101 @@ int dp_vpc_stats_read(dp_ctx_t *c, dp_vpc_stat_t *entries, uint32_t cap, uint32_
   if (reset && ((e = hipMemsetAsync(c->vs_tab, 0, sizeof(dpv::Table), s)) != hipSuccess ||
                 (e = hipStreamSynchronize(s)) != hipSuccess))
     return fail(DP_EIO, "per-VPC statistics reset", e);
+  return 0;
+}
+
+int dp_capture_open(dp_ctx_t *c, const dp_capture_filter_t *filter, uint32_t max_records, uint64_t max_bytes) {
+  if (!c) return fail(DP_EINVAL, "null ctx");
+  if (c->cp_open) return fail(DP_EINVAL, "capture: already open");
+  dpc::Filter f;
+  if (int rc = cp_lower(filter, &f)) return rc;
+  (void)hipSetDevice(c->device);
+  const uint64_t units = max_bytes / 16;
+  hipError_t e;
+  // (an empty array is still an allocation, so the kernels' pointers are never null)
+  if ((e = hipMalloc(&c->cp_state, sizeof(dpc::State))) != hipSuccess ||
+      (e = hipHostMalloc(&c->cp_host, sizeof(dpc::State))) != hipSuccess ||
+      (e = hipMalloc(&c->cp_recs, sizeof(dp_cap_rec_t) * std::max<uint64_t>(max_records, 1))) != hipSuccess ||
+      (e = hipMalloc(&c->cp_bytes, 16 * std::max<uint64_t>(units, 1))) != hipSuccess ||
+      (e = hipMemset(c->cp_state, 0, sizeof(dpc::State))) != hipSuccess ||
+      (e = hipStreamSynchronize(nullptr)) != hipSuccess ||  // (launches come on streams of their own)
+      (e = hipEventCreateWithFlags(&c->cp_used, hipEventDisableTiming)) != hipSuccess) {
+    cp_free(c);
+    return fail(DP_ENOMEM, "capture buffer", e);
+  }
+  c->cp_filter = f;
+  c->cp_max_recs = max_records;
+  c->cp_max_units = units;
+  c->cp_open = true;
+  return 0;
+}
+
+int dp_capture_set_filter(dp_ctx_t *c, const dp_capture_filter_t *filter) {
+  if (!c) return fail(DP_EINVAL, "null ctx");
+  if (!c->cp_open) return fail(DP_EINVAL, "capture: none open");
+  dpc::Filter f;
+  if (int rc = cp_lower(filter, &f)) return rc;
+  c->cp_filter = f;  // (a launch takes its copy as a kernel argument)
+  return 0;
+}
+
+int dp_capture_close(dp_ctx_t *c) {
+  if (!c) return fail(DP_EINVAL, "null ctx");
+  if (!c->cp_open) return 0;
+  (void)hipSetDevice(c->device);
+  cp_free(c);  // waits for the last capture launch
+  return 0;
+}
+
+int dp_capture_device(dp_ctx_t *c, int tap, const uint8_t *dev_buf, uint64_t buf_bytes, const void *dev_recs,
+                      const dp_pkt_meta_t *dev_meta, uint32_t n, void *stream) {
+  if (!c) return fail(DP_EINVAL, "null ctx");
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  reap(c);
+  if (int rc = cp_launch(c, tap, dev_buf, buf_bytes, dev_recs, tap == DP_CAP_TX ? dev_meta : nullptr, n, s)) return rc;
+  if (n == 0) return 0;
+  // dp_capture_read waits for it like for a burst
+  InFlight f;
+  f.done = take_event(c);
+  if (f.done) (void)hipEventRecord(f.done, s);
+  c->inflight.push_back(std::move(f));
+  return 0;
+}
+
+int dp_capture_read(dp_ctx_t *c, dp_cap_rec_t *recs, uint32_t rec_cap, uint8_t *bytes, uint64_t byte_cap,
+                    uint32_t *n_recs, uint64_t *n_bytes, uint64_t *matched, uint64_t *lost, int reset) {
+  if (!c || !n_recs || !n_bytes || (rec_cap && !recs) || (byte_cap && !bytes)) return fail(DP_EINVAL, "null argument");
+  *n_recs = 0;
+  *n_bytes = 0;
+  if (matched) *matched = 0;
+  if (lost) *lost = 0;
+  if (!c->cp_open) return fail(DP_EINVAL, "capture: none open");
+  (void)hipSetDevice(c->device);
+  // on the context's stream, behind every launch not yet known complete
+  hipStream_t s = c->stream;
+  hipError_t e;
+  for (auto &f : c->inflight)
+    if (f.done && (e = hipStreamWaitEvent(s, f.done, 0)) != hipSuccess) return fail(DP_EIO, "stream wait", e);
+  if ((e = hipMemcpyAsync(c->cp_host, c->cp_state, sizeof(dpc::State), hipMemcpyDeviceToHost, s)) != hipSuccess ||
+      (e = hipStreamSynchronize(s)) != hipSuccess)
+    return fail(DP_EIO, "capture counters copy", e);
+  reap(c);
+  const dpc::State st = *c->cp_host;
+  *n_recs = st.n_recs;
+  *n_bytes = st.n_units * 16;
+  if (matched) *matched = st.matched;
+  if (lost) *lost = st.lost;
+  if (st.n_recs > rec_cap || st.n_units * 16 > byte_cap)
+    return fail(DP_ENOSPC, "capture: more records or bytes than the arrays hold");
+  if (st.n_recs && (e = hipMemcpyAsync(recs, c->cp_recs, sizeof(dp_cap_rec_t) * (size_t)st.n_recs,
+                                       hipMemcpyDeviceToHost, s)) != hipSuccess)
+    return fail(DP_EIO, "capture records copy", e);
+  if (st.n_units && (e = hipMemcpyAsync(bytes, c->cp_bytes, 16 * st.n_units, hipMemcpyDeviceToHost, s)) != hipSuccess)
+    return fail(DP_EIO, "capture bytes copy", e);
+  // the clear follows the copies on the same stream and the call returns
+  // after it: no launch of this context falls between them
+  if (reset && dpk_capture_reset(c->cp_state, s)) return fail(DP_EIO, "capture reset", hipGetLastError());
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(DP_EIO, "capture copy", e);
   return 0;
 }
 

@@ -685,6 +685,7 @@ extern "C" uint32_t dpw_sizeof(const char *name) {
       {"dp_ff_input_t", sizeof(dp_ff_input_t)}, {"dp_ff_result_t", sizeof(dp_ff_result_t)},
       {"dp_vpc_stat_t", sizeof(dp_vpc_stat_t)},
       {"dp_fib_key_t", sizeof(dp_fib_key_t)}, {"dp_fib_result_t", sizeof(dp_fib_result_t)},
+      {"dp_capture_filter_t", sizeof(dp_capture_filter_t)}, {"dp_cap_rec_t", sizeof(dp_cap_rec_t)},
       {"dp_tables_desc_t", sizeof(dp_tables_desc_t)}, {"dp_pkt_in_t", sizeof(dp_pkt_in_t)},
       {"dp_pkt_out_t", sizeof(dp_pkt_out_t)}, {"dp_pkt_meta_t", sizeof(dp_pkt_meta_t)},
       {"dp_flow_key_t", sizeof(dp_flow_key_t)},

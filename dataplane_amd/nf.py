@@ -291,6 +291,52 @@ class GpuPathNf:
                 "dp_vpc_stats_read", self.lib)
         return cells[:n.value].copy(), int(lost.value)
 
+    # -- packet capture (the PacketDumper stage, pipeline/src/sample_nfs.rs:41-150) --
+    @staticmethod
+    def _filter_ptr(flt):
+        if flt is None:
+            return None, None
+        keep = np.ascontiguousarray(np.atleast_1d(flt), dtype=A.CAP_FILTER)
+        return keep, keep.ctypes.data
+
+    def capture_open(self, flt, max_records: int, max_bytes: int) -> None:
+        """dp_capture_open: a capture buffer of max_records records and max_bytes
+        bytes on the device; `flt` an A.CAP_FILTER record (None: every packet)."""
+        keep, ptr = self._filter_ptr(flt)
+        A.check(self.lib.dp_capture_open(self.ctx, ptr, max_records, max_bytes), "dp_capture_open", self.lib)
+        self._cap = (max_records, max_bytes)
+
+    def set_capture_filter(self, flt) -> None:
+        """dp_capture_set_filter: the filter of the launches that follow."""
+        keep, ptr = self._filter_ptr(flt)
+        A.check(self.lib.dp_capture_set_filter(self.ctx, ptr), "dp_capture_set_filter", self.lib)
+
+    def set_capture(self, taps: int) -> None:
+        """dp_ctx_set_option(DP_OPT_CAPTURE): the taps (A.CAP_RX | A.CAP_TX) every
+        process_device burst runs while a capture is open; 0 switches them off."""
+        self.set_option(A.OPT_CAPTURE, taps)
+
+    def capture_device(self, tap: int, dev_buf: int, buf_bytes: int, dev_recs: int, dev_meta: Optional[int],
+                       n: int, stream: Optional[int] = None) -> None:
+        """The stage alone over n device-resident records (dp_capture_device):
+        raw device pointers; dp_pkt_in_t records for A.CAP_RX, dp_pkt_out_t for A.CAP_TX."""
+        A.check(self.lib.dp_capture_device(self.ctx, tap, dev_buf, buf_bytes, dev_recs, dev_meta, n, stream),
+                "dp_capture_device", self.lib)
+
+    def capture_read(self, reset: bool = False):
+        """(A.CAP_REC records, their bytes as a uint8 array, matched, lost) of
+        dp_capture_read; `reset` empties the buffer with the read."""
+        max_records, max_bytes = self._cap
+        recs, data = np.zeros(max_records, dtype=A.CAP_REC), np.zeros(max_bytes, dtype=np.uint8)
+        nr, nb, matched, lost = C.c_uint32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        A.check(self.lib.dp_capture_read(self.ctx, recs.ctypes.data, max_records, data.ctypes.data, max_bytes,
+                                         C.byref(nr), C.byref(nb), C.byref(matched), C.byref(lost),
+                                         1 if reset else 0), "dp_capture_read", self.lib)
+        return recs[:nr.value].copy(), data[:nb.value].copy(), int(matched.value), int(lost.value)
+
+    def capture_close(self) -> None:
+        A.check(self.lib.dp_capture_close(self.ctx), "dp_capture_close", self.lib)
+
     def close(self) -> None:
         if self.ctx:
             self.lib.dp_ctx_destroy(self.ctx)

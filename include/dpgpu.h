@@ -632,7 +632,19 @@ enum dp_ctx_option {
      * zero-copy host path, dp_process_mbufs) the stage reads them back over
      * PCIe: 16 B a packet, 24 B with a caller's meta array.
      * 0 (default): no launch, no allocation. */
-    DP_OPT_VPC_STATS = 3
+    DP_OPT_VPC_STATS = 3,
+    /* A mask of enum dp_cap_tap ("Packet capture" below): while a capture is
+     * open, every dp_process_burst_device of the context runs the RX tap on
+     * the burst's stream before the path and / or the TX tap after the last
+     * kernel that writes the records, behind the Stats stage.  A tap the
+     * filter cannot run on (DP_CAPF_DONE or a VNI clause on the RX tap) fails
+     * the burst whole with DP_EINVAL; a TX tap with a VNI clause on a burst
+     * without a meta array reads the context's meta scratch, as the Stats
+     * stage does.  The host-origin entry points (dp_process_burst, _sharded,
+     * dp_process_mbufs) ignore the option: their caller has the frames on the
+     * host already.  0 (default), or no capture open: no launch, no
+     * allocation. */
+    DP_OPT_CAPTURE = 4
 };
 enum dp_host_path { DP_HOST_AUTO = 0, DP_HOST_COPY = 1, DP_HOST_ZERO_COPY = 2 };
 int dp_ctx_set_option(dp_ctx_t *ctx, int option, int64_t value);
@@ -1054,6 +1066,116 @@ int dp_vpc_stats_accumulate_device(dp_ctx_t *ctx, const dp_pkt_out_t *dev_out,
  * far and before the call returns, so no update falls between the two. */
 int dp_vpc_stats_read(dp_ctx_t *ctx, dp_vpc_stat_t *entries, uint32_t cap, uint32_t *n_entries,
                       uint64_t *lost_packets, int reset);
+
+/* ------------------------------------------------------------------------ */
+/* Packet capture: the reference's PacketDumper (pipeline/src/sample_nfs.rs: */
+/* 41-150), a switchable tap with an optional filter, on the device.  A      */
+/* declarative filter selects packets of a device-resident burst; the        */
+/* selected packets are appended, in burst order, to a context-owned capture */
+/* buffer in device memory: a dp_cap_rec_t each and the frames' bytes packed  */
+/* densely in 16-byte units.  The buffer is cumulative across launches until  */
+/* read with reset.  enable / disable are DP_OPT_CAPTURE, set_filter is       */
+/* dp_capture_set_filter, the sample filters are dp_capture_filter_t values   */
+/* (INTEGRATION.md).                                                          */
+/*                                                                            */
+/* Frame of a packet.  RX tap: in.off / in.len.  TX tap: out.off / out.len    */
+/* when out.done == DP_DONE_DELIVERED; a packet that was not delivered has no */
+/* frame: its header clauses (L4, SRC, DST, SPORT, DPORT) are false, and if   */
+/* the remaining clauses select it, it is recorded with caplen 0 and len =    */
+/* out.len ("everything the ACL dropped for VNI 3000").  A frame that         */
+/* violates the layout contract of dp_process_burst_device (its end rounded   */
+/* up to 16 bytes outside buf_bytes; on the RX tap also off < DP_HEADROOM) is */
+/* treated the same way, as no frame, and never read.                         */
+/*                                                                            */
+/* The filter's view of a frame is a small parse of its own over the          */
+/* outermost headers -- not Headers::parse; exact for the frames the          */
+/* reference's sample filters tell apart, and this is its boundary:           */
+/*   Ethernet: up to two tags (0x8100 / 0x88a8), then IPv4 (0x0800) or IPv6   */
+/*     (0x86dd); anything else (a third tag, ARP, a frame cut short) is in no */
+/*     class and has no addresses.                                            */
+/*   IPv4: IHL >= 5 and the whole header inside the frame (the version nibble */
+/*     is not examined); a non-zero fragment offset gives no ports and no     */
+/*     class (the addresses stay).                                            */
+/*   IPv6: the fixed header inside the frame; at most three extension         */
+/*     headers are skipped: kinds 0, 43 and 60 are (len + 1) * 8 bytes, kind  */
+/*     44 is 8 bytes and a non-zero fragment offset is handled as for IPv4;   */
+/*     an extension header cut by the frame's end, or a fourth one, gives no  */
+/*     class.                                                                 */
+/*   Classes: UDP (protocol 17), TCP (6), ICMP4 (IPv4, 1), ICMP6 (IPv6, 58),  */
+/*     VXLAN (UDP with ports and source or destination port 4789).            */
+/*   Ports exist (UDP / TCP) when their four bytes lie inside the frame.      */
+/*   A prefix clause of the other family is false.                            */
+/*                                                                            */
+/* Order and capacity.  Records appear in launch order and, within a launch,  */
+/* in packet order.  Record k of a launch is kept if and only if it and every */
+/* earlier one fit in both max_records and max_bytes (max_bytes rounded down  */
+/* to 16), a record taking caplen rounded up to 16 bytes: what is kept is     */
+/* always an exact prefix; `lost` counts the rest, `matched` counts both.     */
+/* Bytes past caplen in a record's last 16-byte unit are zero.                */
+/* Concurrency.  Capture launches of one context run one after the other,     */
+/* whatever their streams (they share the launch scratch and the buffer).     */
+/* ------------------------------------------------------------------------ */
+enum dp_cap_tap { DP_CAP_RX = 1, DP_CAP_TX = 2 };   /* before / after the path */
+
+/* packet classes (not exclusive): a packet matches DP_CAPF_L4 when it is in any class of l4_mask */
+enum dp_cap_class { DP_CAPC_UDP = 1, DP_CAPC_TCP = 2, DP_CAPC_ICMP4 = 4, DP_CAPC_ICMP6 = 8,
+                    DP_CAPC_VXLAN = 16 /* UDP with source or destination port 4789 */ };
+
+enum dp_capf { DP_CAPF_L4 = 1, DP_CAPF_SRC = 2, DP_CAPF_DST = 4, DP_CAPF_SPORT = 8, DP_CAPF_DPORT = 16,
+               DP_CAPF_DONE = 32, DP_CAPF_SRC_VNI = 64, DP_CAPF_DST_VNI = 128 };
+
+typedef struct dp_capture_filter {
+    uint32_t clauses;            /* enum dp_capf: every set clause must hold; 0 = every packet */
+    uint32_t l4_mask;            /* enum dp_cap_class */
+    uint64_t done_mask;          /* bit d: out.done == d (TX tap only) */
+    uint32_t src_vni, dst_vni;   /* meta.src_vni / dst_vni equal (TX tap with a meta array only) */
+    dp_prefix_t src, dst;        /* outermost IP source / destination inside the prefix */
+    uint16_t sport_lo, sport_hi, dport_lo, dport_hi;   /* inclusive, UDP / TCP only */
+    uint32_t snaplen;            /* bytes kept per frame; 0 = the whole frame */
+    uint32_t pad;
+} dp_capture_filter_t;           /* 80 B */
+
+typedef struct dp_cap_rec {      /* 32 B */
+    uint64_t off;                /* into the capture bytes, a multiple of 16 */
+    uint32_t burst;              /* capture launches since open / reset, from 0 */
+    uint32_t index;              /* the packet's index in that burst */
+    uint16_t len, caplen;        /* frame length; bytes stored (min(len, snaplen)) */
+    uint8_t tap, done;           /* done: DP_DONE_NONE on the RX tap */
+    uint16_t pad;
+    uint32_t src_vni, dst_vni;   /* TX tap with a meta array, else 0 */
+} dp_cap_rec_t;
+
+/* Open the context's capture: a buffer of max_records records and max_bytes
+ * bytes in device memory, empty; `filter` NULL selects every packet.  One
+ * capture a context (DP_EINVAL while one is open; also for an unknown clause,
+ * or a prefix clause whose family is not 4 / 6 or whose length exceeds it). */
+int dp_capture_open(dp_ctx_t *, const dp_capture_filter_t *, uint32_t max_records, uint64_t max_bytes);
+/* Another filter for the launches that follow (launches already enqueued
+ * keep theirs). */
+int dp_capture_set_filter(dp_ctx_t *, const dp_capture_filter_t *);  /* for launches that follow */
+/* Waits for the last capture launch and frees the buffer; what was not read
+ * is gone. */
+int dp_capture_close(dp_ctx_t *);
+/* The stage alone over n device-resident records on `stream` (as in
+ * dp_process_burst_device; asynchronous there), whatever DP_OPT_CAPTURE is:
+ * `dev_buf` 16-byte aligned under the layout contract above, `dev_recs` the
+ * burst's dp_pkt_in_t (DP_CAP_RX) or dp_pkt_out_t (DP_CAP_TX) records,
+ * 16-byte aligned.  DP_EINVAL: no capture open, another tap, DP_CAPF_DONE or a
+ * VNI clause on the RX tap, a VNI clause with dev_meta NULL.  n = 0 is DP_OK
+ * and counts no launch. */
+int dp_capture_device(dp_ctx_t *, int tap, const uint8_t *dev_buf, uint64_t buf_bytes,
+                      const void *dev_recs /* dp_pkt_in_t (RX) or dp_pkt_out_t (TX) */,
+                      const dp_pkt_meta_t *dev_meta /* may be NULL */, uint32_t n, void *stream);
+/* Read the buffer, like dp_vpc_stats_read: synchronous, ordered behind every
+ * burst and capture launch the context has launched.  `*n_recs` / `*n_bytes`
+ * receive what the buffer holds, `matched` / `lost` (may be NULL) the packets
+ * selected since open / reset and those of them that did not fit.  With
+ * rec_cap or byte_cap too small nothing is copied or reset and the call
+ * returns DP_ENOSPC (the counts say what is needed).  `reset` != 0 empties the
+ * buffer and the counters on the stream after the copy, before the call
+ * returns; the next launch's `burst` is 0. */
+int dp_capture_read(dp_ctx_t *, dp_cap_rec_t *recs, uint32_t rec_cap, uint8_t *bytes, uint64_t byte_cap,
+                    uint32_t *n_recs, uint64_t *n_bytes, uint64_t *matched, uint64_t *lost, int reset);
 
 /* Introspection: bytes of the device table image and its parts (for
  * DESIGN.md / bench), and the last HIP error string. */

@@ -6487,6 +6487,18 @@ __global__ void __launch_bounds__(256) dp_flow_apply(dpf::FlowCtx fc) {
   }
 }
 
+// The counters a flows launch starts from zero -- the event count, the
+// sensitive-verdict count, the NAT pass's words -- in one launch (they head
+// three arrays; three fill kernels before)
+__global__ void __launch_bounds__(64) dp_flow_clear(dpf::FlowCtx fc) {
+  const uint32_t t = threadIdx.x;
+  if (t == 0) {
+    fc.events[0] = 0;
+    fc.sens[0] = 0;
+  }
+  for (uint32_t k = t; k < DPF_CNT_WORDS; k += 64) fc.pf_cnt[k] = 0;
+}
+
 // Sum (and clear) the partial histograms into the caller's DoneReason
 // counts: block r sums reason r's DPD_STAT_SLOTS partials.
 __global__ void __launch_bounds__(DPD_STAT_SLOTS) dp_stats_reduce(unsigned long long *__restrict__ part,
@@ -6777,9 +6789,7 @@ extern "C" int dpk_launch_pipeline_flows(const uint8_t *img_base, const void *im
                                          hipEvent_t fork, hipEvent_t fork2, hipEvent_t join, int fork_at) {
   if (n == 0) return 0;
   dpf::FlowCtx fc = *reinterpret_cast<const dpf::FlowCtx *>(fc_host);
-  if (hipMemsetAsync(fc.events, 0, sizeof(uint32_t), stream) != hipSuccess) return -5;
-  if (hipMemsetAsync(fc.sens, 0, sizeof(uint32_t), stream) != hipSuccess) return -5;
-  if (hipMemsetAsync(fc.pf_cnt, 0, sizeof(uint32_t) * DPF_CNT_WORDS, stream) != hipSuccess) return -5;
+  hipLaunchKernelGGL(dp_flow_clear, dim3(1), dim3(64), 0, stream, fc);
   const Image *im = reinterpret_cast<const Image *>(image_dev);
   uint32_t blocks = (n + TPB - 1) / TPB;
   unsigned long long *part = stats ? reinterpret_cast<unsigned long long *>(stats_part) : nullptr;

@@ -182,6 +182,7 @@ std::atomic<uint32_t> g_nat_seq{0};  // dpf_debug_nat_sequential
 std::atomic<uint32_t> g_flows_full{0};  // dpf_debug_flows_full
 std::atomic<uint32_t> g_last_lean{0};   // dpf_debug_last_lean
 std::atomic<uint32_t> g_no_ctx{0};      // dpf_debug_no_ctx
+std::atomic<uint32_t> g_part_waits{0};  // dpd_debug_part_waits
 // where the NAT pass forks the replay of the records off the allocating lane
 // to the side stream: 0 never (one replay after the lane), 1 after the
 // resolve, 2 after the lane's plan, 3 the steady refreshes after dp_nat_prep
@@ -215,8 +216,11 @@ struct InFlight {
 
 // DoneReason partial histograms: a small ring of buffers, one per launch.
 // A slot is reused only after the launch that used it (kernel + reduce) has
-// completed: the new launch's stream waits on the slot's event, so bursts on
-// different streams never share partial counters.
+// completed, so bursts on different streams never share partial counters: a
+// slot remembers the stream and the in-flight entry's completion event of its
+// last use.  The same stream again is ordered by the stream itself; another
+// stream waits on that event (none once the entry has been reaped: the launch
+// is known complete).
 constexpr int kPartSlots = 4;
 
 // Host-origin bursts are moved in chunks of at least kHostChunk packets on
@@ -228,8 +232,8 @@ constexpr int kHostStreams = 3;
 class HostPool;
 struct PartSlot {
   uint64_t *part = nullptr;
-  hipEvent_t used = nullptr;
-  bool armed = false;
+  hipStream_t stream = nullptr;  // of the slot's last launch
+  hipEvent_t done = nullptr;     // that launch's InFlight::done while it is in flight (not owned)
 };
 
 }  // namespace
@@ -333,7 +337,11 @@ void reap(dp_ctx *c) {
   while (!c->inflight.empty()) {
     InFlight &f = c->inflight.front();
     if (f.done && hipEventQuery(f.done) == hipErrorNotReady) break;
-    if (f.done) c->spare.push_back(f.done);
+    if (f.done) {
+      for (auto &ps : c->parts)
+        if (ps.done == f.done) ps.done = nullptr;  // (the event goes on to another launch)
+      c->spare.push_back(f.done);
+    }
     c->inflight.pop_front();
   }
 }
@@ -661,11 +669,9 @@ int dp_ctx_create(int device_ordinal, dp_ctx_t **out) {
   if ((e = hipMalloc(&c->d_stats, sizeof(uint64_t) * DP_DONE_COUNT)) != hipSuccess)
     return fail(DP_ENOMEM, "hipMalloc stats", e);
   const size_t part_bytes = sizeof(uint64_t) * DP_DONE_COUNT * DPD_STAT_SLOTS;
-  for (auto &ps : c->parts) {
+  for (auto &ps : c->parts) {  // (zeroed once: dp_stats_reduce leaves them zero)
     if ((e = hipMalloc(&ps.part, part_bytes)) != hipSuccess) return fail(DP_ENOMEM, "hipMalloc stats partials", e);
     if ((e = hipMemset(ps.part, 0, part_bytes)) != hipSuccess) return fail(DP_EIO, "clear stats partials", e);
-    if ((e = hipEventCreateWithFlags(&ps.used, hipEventDisableTiming)) != hipSuccess)
-      return fail(DP_EIO, "hipEventCreate", e);
   }
   *out = c.release();
   return 0;
@@ -684,8 +690,7 @@ int dp_ctx_destroy(dp_ctx_t *c) {
   c->inflight.clear();
   for (hipEvent_t e : c->spare) (void)hipEventDestroy(e);
   for (auto &ps : c->parts) {
-    if (ps.used) { (void)hipEventSynchronize(ps.used); (void)hipEventDestroy(ps.used); }
-    if (ps.part) (void)hipFree(ps.part);
+    if (ps.part) (void)hipFree(ps.part);  // (its last launch: an in-flight entry, waited for above)
   }
   if (c->d_buf) (void)hipFree(c->d_buf);
   if (c->d_in) (void)hipFree(c->d_in);
@@ -861,9 +866,36 @@ static int launch_burst(dp_ctx_t *c, uint8_t *dev_buf, uint64_t buf_bytes, const
   if (dev_stats) {
     ps = &c->parts[c->next_part];
     c->next_part = (c->next_part + 1) % kPartSlots;
-    if (ps->armed && hipStreamWaitEvent(s, ps->used, 0) != hipSuccess) return fail(DP_EIO, "stream wait");
+    // (hipStreamPerThread is one handle for every thread's own stream: equal
+    // handles do not mean one stream there)
+    if (ps->done && (ps->stream != s || s == hipStreamPerThread)) {
+      if (hipStreamWaitEvent(s, ps->done, 0) != hipSuccess) return fail(DP_EIO, "stream wait");
+      g_part_waits.fetch_add(1, std::memory_order_relaxed);
+    }
     part = ps->part;
   }
+  // The launch's one marker, on every way out from here (whatever this call
+  // enqueues on `s` may read the image and, with a histogram, write the part
+  // slot): it retires the image and frees the slot for another stream.
+  struct Marker {
+    dp_ctx *c;
+    hipStream_t s;
+    PartSlot *ps;
+    std::shared_ptr<DevImage> img;
+    ~Marker() {
+      InFlight f;
+      f.img = std::move(img);
+      f.done = take_event(c);
+      const bool marked = f.done && hipEventRecord(f.done, s) == hipSuccess;
+      if (ps) {
+        // (no marker to wait on: the slot's next user must find the launch over)
+        if (!marked) (void)hipStreamSynchronize(s);
+        ps->stream = s;
+        ps->done = marked ? f.done : nullptr;
+      }
+      c->inflight.push_back(std::move(f));
+    }
+  } marker{c, s, ps, img};
   int rc;
   if (c->ft) {
     // the flows variant: FlowLookup on the attached table and the flow-aware
@@ -1035,16 +1067,7 @@ static int launch_burst(dp_ctx_t *c, uint8_t *dev_buf, uint64_t buf_bytes, const
       return crc;
     }
   }
-  if (ps) {
-    (void)hipEventRecord(ps->used, s);
-    ps->armed = true;
-  }
-  InFlight f;
-  f.img = img;
-  f.done = take_event(c);
-  if (f.done) (void)hipEventRecord(f.done, s);
-  c->inflight.push_back(std::move(f));
-  return 0;
+  return 0;  // (the marker is recorded on the way out)
 }
 
 int dp_process_burst_device(dp_ctx_t *c, uint8_t *dev_buf, uint64_t buf_bytes,
@@ -1330,6 +1353,9 @@ void dpf_debug_flows_full(int on) { g_flows_full.store(on ? 1u : 0u, std::memory
 // Test hook (not part of dpgpu.h): 1 runs the non-flow pipeline without the
 // LDS copy of the context tables even where they fit (A/Bs, parity of both).
 void dpf_debug_no_ctx(int on) { g_no_ctx.store(on ? 1u : 0u, std::memory_order_relaxed); }
+// Test hook (not part of dpgpu.h): how many launches so far took a part slot
+// whose last launch was still in flight on another stream and waited for it.
+int dpd_debug_part_waits() { return (int)g_part_waits.load(std::memory_order_relaxed); }
 // Test hook (not part of dpgpu.h): where the NAT pass forks the replay off the
 // allocating lane (0 never, 1 after the resolve, 2 after the lane's plan, 3
 // the steady refreshes after dp_nat_prep and the rest after the plan;

@@ -567,7 +567,12 @@ int dp_process_burst(dp_ctx_t *ctx, uint8_t *buf, uint64_t buf_bytes,
  * `dev_meta` (may be NULL: the bench path writes only the 16-byte out
  * records) receives the rest of each PacketMeta, flow_info included.
  * `dev_stats` (may be NULL) is accumulated into (DP_DONE_COUNT u64).
- * Bursts of one context may run concurrently on different streams. */
+ * Bursts of one context may run concurrently on different streams.  The
+ * context tells streams apart by their handles (hipStreamPerThread is taken
+ * as a different stream every time): a caller that destroys a stream while
+ * one of the context's bursts with `dev_stats` is still running on it must
+ * not hand the context a new stream before that burst has completed, since
+ * the new handle may equal the old one. */
 int dp_process_burst_device(dp_ctx_t *ctx, uint8_t *dev_buf, uint64_t buf_bytes,
                             const dp_pkt_in_t *dev_in, dp_pkt_out_t *dev_out,
                             dp_pkt_meta_t *dev_meta, uint32_t n, uint64_t *dev_stats,

@@ -268,7 +268,8 @@ GPU_SYMBOLS = ["dp_abi_version", "dp_ctx_create", "dp_ctx_destroy", "dp_tables_p
                "dp_ff_classify_device", "dp_ff_key_from_match", "dp_ff_classify_match",
                "dp_vpc_stats_accumulate_device", "dp_vpc_stats_read", "dp_fib_lookup",
                "dp_fib_lookup_device", "dp_capture_open", "dp_capture_set_filter",
-               "dp_capture_close", "dp_capture_device", "dp_capture_read"]
+               "dp_capture_close", "dp_capture_device", "dp_capture_read",
+               "dp_flow_filter_match", "dp_flow_snapshot", "dp_flow_snapshot_device"]
 # dp_acl_key_t / dp_acl_result_t (the ACL classifier alone)
 ACL_KEY = np.dtype([("src_vni", "<u4"), ("dst_vni", "<u4"), ("family", "u1"), ("proto", "u1"),
                     ("sport", "<u2"), ("dport", "<u2"), ("pad", "u1", 2), ("src", "u1", 16),
@@ -316,7 +317,20 @@ CAP_RX, CAP_TX = 1, 2                                                    # enum 
 CAPC_UDP, CAPC_TCP, CAPC_ICMP4, CAPC_ICMP6, CAPC_VXLAN = 1, 2, 4, 8, 16  # enum dp_cap_class
 (CAPF_L4, CAPF_SRC, CAPF_DST, CAPF_SPORT, CAPF_DPORT, CAPF_DONE, CAPF_SRC_VNI,
  CAPF_DST_VNI) = (1 << i for i in range(8))                              # enum dp_capf
-NP_STRUCTS = dict(dp_flow_key_t=FLOW_KEY, dp_flow_t=FLOW, dp_flow_info_t=FLOW_INFO, dp_acl_key_t=ACL_KEY,
+# flow-table snapshot (include/dpgpu.h "Flow-table snapshot": FlowTable::snapshot(filter),
+# flow-entry/src/flow_table/table.rs:319-372): dp_flow_filter_t / dp_flow_entry_t
+FLOW_FILTER = np.dtype([("clauses", "<u4"), ("src_vni", "<u4"), ("dst_vni", "<u4"), ("family", "u1"),
+                        ("kind_mask", "u1"), ("status_mask", "u1"), ("nat_mask", "u1"), ("flags_all", "<u4"),
+                        ("flags_none", "<u4"), ("sport_lo", "<u2"), ("sport_hi", "<u2"), ("dport_lo", "<u2"),
+                        ("dport_hi", "<u2"), ("nat_port_lo", "<u2"), ("nat_port_hi", "<u2"), ("src", _PREFIX),
+                        ("dst", _PREFIX), ("nat_ip", _PREFIX), ("genid", "<i8"), ("expires_at", "<u8")])
+FLOW_ENTRY = np.dtype([("key", FLOW_KEY), ("slot", "<u4"), ("info", FLOW_INFO)])
+assert FLOW_FILTER.itemsize == 112 and FLOW_ENTRY.itemsize == 136
+FLOWF = {n: 1 << i for i, n in enumerate(                                # enum dp_flowf
+    ["SRC_VNI", "DST_VNI", "FAMILY", "KIND", "SRC", "DST", "SPORT", "DPORT", "STATUS", "FLAGS_ALL",
+     "FLAGS_NONE", "GENID_LT", "GENID_EQ", "EXPIRES_LE", "NAT", "NAT_IP", "NAT_PORT"])}
+FLOW_NAT_PF, FLOW_NAT_MASQ, FLOW_NAT_MASQ_ALLOC = 1, 2, 4                # enum dp_flow_nat
+NP_STRUCTS = dict(dp_flow_filter_t=FLOW_FILTER, dp_flow_entry_t=FLOW_ENTRY, dp_flow_key_t=FLOW_KEY, dp_flow_t=FLOW, dp_flow_info_t=FLOW_INFO, dp_acl_key_t=ACL_KEY,
                   dp_acl_result_t=ACL_RESULT, dp_ff_input_t=FF_INPUT, dp_ff_result_t=FF_RESULT,
                   dp_vpc_stat_t=VPC_STAT, dp_fib_key_t=FIB_KEY, dp_fib_result_t=FIB_RESULT,
                   dp_capture_filter_t=CAP_FILTER, dp_cap_rec_t=CAP_REC)
@@ -440,6 +454,10 @@ def gpu_lib() -> C.CDLL:
         lib.dp_capture_read.argtypes = [_VP, _VP, C.c_uint32, _VP, C.c_uint64, C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                         C.POINTER(C.c_uint64), C.c_int]
+        lib.dp_flow_filter_match.argtypes = [_VP, _VP, _VP]
+        lib.dp_flow_snapshot.argtypes = [_VP, _VP, C.POINTER(C.c_uint64), _VP, C.c_uint32,
+                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        lib.dp_flow_snapshot_device.argtypes = lib.dp_flow_snapshot.argtypes
         lib.dpd_debug_set_fib_lookup_form.argtypes = [C.c_int]
         lib.dpd_debug_classify_copies.argtypes = [C.c_int]
         lib.dpd_debug_hip_runtimes.restype = C.c_int

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/dpgpu.h"
+#include "dp_flows_dev.h"
 #include "dp_flows_rt.h"
 #include "dp_masq.h"
 
@@ -29,7 +30,12 @@ using dpf::FKey;
 
 namespace {
 
-constexpr uint32_t kTB = 256;
+// (shared with the snapshot unit: dp_flows_dev.h)
+using dpfl::kTB;
+using dpfl::fill_info;
+using dpfl::key_words;
+using dpfl::run;
+using dpfl::blocks_for;
 
 // FlowTable::lookup by key: linear probing from the key's home slot, at most
 // max_probe + 1 slots (no stored flow sits further from its home)
@@ -54,41 +60,6 @@ __device__ __forceinline__ uint32_t probe(const FlowSlot *slots, uint32_t mask, 
 __device__ __forceinline__ bool ref_live(const FlowSlot *slots, uint32_t mask, uint64_t ref) {
   const uint32_t sl = (uint32_t)ref;
   return ref != ~0ull && sl <= mask && slots[sl].state == ((uint32_t)(ref >> 32) << 2 | dpf::FS_FULL);
-}
-
-__device__ void fill_info(const FlowSlot *slots, uint32_t mask, uint32_t sl, dp_flow_info_t &o) {
-  const FlowSlot &s = slots[sl];
-  o.ref = dpf::make_ref(sl, s.state);
-  o.status = s.status;
-  o.flags = s.flags;
-  o.dst_vni = s.dst_vni;
-  o.pad = 0;
-  o.genid = s.genid;
-  o.expires_at = s.expires_at;
-  o.related = DP_FLOW_NONE;
-  if (s.related <= mask && slots[s.related].state == s.related_tag)
-    o.related = dpf::make_ref(s.related, s.related_tag);
-  o.flags = s.flags & 7u;
-  if (s.flags & dpf::kFlagMasq) {  // MasqueradeState (nat/src/masquerade/state.rs:13-20)
-    o.masq = (uint8_t)(s.pf & 0xffu);
-    o.pf_status = (uint8_t)((s.pf >> 8) & 0xffu);
-    o.pf_port = (uint16_t)(s.pf >> 16);
-    o.pf_family = (uint8_t)s.pf_fam;
-    for (int j = 0; j < 4; j++)
-      for (int b = 0; b < 4; b++) o.pf_ip[4 * j + b] = (uint8_t)(s.pf_ip[j] >> (24 - 8 * b));
-    if (s.pf_fam == 4) for (int b = 4; b < 16; b++) o.pf_ip[b] = 0;
-    o.masq_alloc = s.mq_rec != 0;
-    o.idle_timeout_s = s.pf_rule;
-  }
-  if (s.flags & dpf::kFlagPf) {  // PortFwState (nat/src/portfw/flow_state.rs:29-35)
-    o.pf = (uint8_t)(s.pf & 0xffu);
-    o.pf_status = (uint8_t)((s.pf >> 8) & 0xffu);
-    o.pf_port = (uint16_t)(s.pf >> 16);
-    o.pf_rule = s.pf_rule;
-    o.pf_family = (uint8_t)s.pf_fam;
-    for (int j = 0; j < 4; j++)
-      for (int b = 0; b < 4; b++) o.pf_ip[4 * j + b] = (uint8_t)(s.pf_ip[j] >> (24 - 8 * b));
-  }
 }
 
 // A flow leaving the table drops its FlowInfo, and with it the allocation its
@@ -371,20 +342,6 @@ __global__ void __launch_bounds__(kTB) fl_count_k(const FlowSlot *slots, uint64_
 // --------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------
-FKey key_words(const dp_flow_key_t &x) {
-  FKey k{};
-  k.w[0] = x.src_vni;
-  k.w[1] = (uint32_t)x.family | ((uint32_t)x.kind << 8);
-  k.w[2] = ((uint32_t)x.sport << 16) | x.dport;
-  uint8_t s[16] = {0}, d[16] = {0};
-  const size_t n = x.family == 4 ? 4 : 16;
-  memcpy(s, x.src, n);
-  memcpy(d, x.dst, n);
-  memcpy(&k.w[3], s, 16);
-  memcpy(&k.w[7], d, 16);
-  return k;
-}
-
 // What a FlowInfo can hold here (same checks as the oracle's flow_check).
 bool flow_valid(const dp_flow_t &f) {
   const dp_flow_key_t &x = f.key;
@@ -399,24 +356,6 @@ bool flow_valid(const dp_flow_t &f) {
 }
 
 using Scratch = FlowScratch;
-
-// Run `f(stream)` with the table's device current and its stream; sync.
-template <class F>
-int run(dp_flow_table *ft, const char *what, F f) {
-  int prev = 0;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(ft->device);
-  // after every flows burst launched before this call (dp_flows_rt.h)
-  if (ft->burst_armed) (void)hipStreamWaitEvent(ft->stream, ft->last_burst, 0);
-  int rc = f(ft->stream);
-  hipError_t e = hipStreamSynchronize(ft->stream);
-  if (!rc && e != hipSuccess) rc = dpr_fail(DP_EIO, what, e);
-  if (!rc && (e = hipGetLastError()) != hipSuccess) rc = dpr_fail(DP_EIO, what, e);
-  (void)hipSetDevice(prev);
-  return rc;
-}
-
-uint32_t blocks_for(uint64_t n) { return (uint32_t)((n + kTB - 1) / kTB); }
 
 // A management call's release list for `cap` departures (counter zeroed on
 // the stream); no list when the table has no allocator.  false: no memory.

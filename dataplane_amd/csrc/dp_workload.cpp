@@ -690,6 +690,7 @@ extern "C" uint32_t dpw_sizeof(const char *name) {
       {"dp_pkt_out_t", sizeof(dp_pkt_out_t)}, {"dp_pkt_meta_t", sizeof(dp_pkt_meta_t)},
       {"dp_flow_key_t", sizeof(dp_flow_key_t)},
       {"dp_flow_t", sizeof(dp_flow_t)}, {"dp_flow_info_t", sizeof(dp_flow_info_t)},
+      {"dp_flow_filter_t", sizeof(dp_flow_filter_t)}, {"dp_flow_entry_t", sizeof(dp_flow_entry_t)},
       {"dp_mbuf_layout_t", sizeof(dp_mbuf_layout_t)},
   };
   for (auto &e : tab)

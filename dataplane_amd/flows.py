@@ -61,6 +61,70 @@ def make_flow(key: np.ndarray, dst_vni: int, flags: int = 0, genid: int = 0,
     return f
 
 
+def _prefix(rec, text) -> None:
+    net = ipaddress.ip_network(text, strict=False)
+    b = net.network_address.packed
+    rec["family"], rec["len"] = 4 if net.version == 4 else 6, net.prefixlen
+    rec["addr"] = np.frombuffer(b + bytes(16 - len(b)), np.uint8)
+
+
+def _mask(v) -> int:
+    return 1 << v if isinstance(v, (int, np.integer)) else sum({1 << int(x) for x in v})
+
+
+def _range(v) -> tuple:
+    return (v, v) if isinstance(v, (int, np.integer)) else (v[0], v[1])
+
+
+def flow_filter(**clauses) -> np.ndarray:
+    """A dp_flow_filter_t (include/dpgpu.h "Flow-table snapshot"): every clause
+    given must hold, none selects every flow.  ``src_vni``, ``dst_vni``,
+    ``family``; ``kind`` / ``status``: one value or several; ``src``, ``dst``,
+    ``nat_ip``: prefixes as text; ``sport``, ``dport``, ``nat_port``: a value
+    or an inclusive (lo, hi); ``flags_all``, ``flags_none``: masks of
+    FLOW_* flags; ``genid_lt`` or ``genid_eq``; ``expires_le``; ``nat``: a
+    mask of FLOW_NAT_*."""
+    f = np.zeros((), dtype=A.FLOW_FILTER)
+    if "genid_lt" in clauses and "genid_eq" in clauses:
+        raise ValueError("genid_lt and genid_eq share the filter's genid")
+    for name, v in clauses.items():
+        clause = {"kind": "KIND", "status": "STATUS", "expires_le": "EXPIRES_LE"}.get(name, name.upper())
+        if clause not in A.FLOWF:
+            raise ValueError(f"unknown flow filter clause {name!r}")
+        f["clauses"] |= A.FLOWF[clause]
+        if name in ("kind", "status"):
+            f[name + "_mask"] = _mask(v)
+        elif name in ("src", "dst", "nat_ip"):
+            _prefix(f[name], v)
+        elif name in ("sport", "dport", "nat_port"):
+            f[name + "_lo"], f[name + "_hi"] = _range(v)
+        elif name in ("genid_lt", "genid_eq"):
+            f["genid"] = v
+        else:
+            f[{"expires_le": "expires_at", "nat": "nat_mask"}.get(name, name)] = v
+    return f
+
+
+def _filter_ptr(filter):
+    """(keep-alive array, pointer) of an optional filter record."""
+    if filter is None:
+        return None, None
+    a = np.ascontiguousarray(filter, dtype=A.FLOW_FILTER)
+    return a, a.ctypes.data
+
+
+def filter_match(filter, key: np.ndarray, info: np.ndarray) -> bool:
+    """dp_flow_filter_match: the filter's predicate on the host (no device);
+    ValueError for an invalid filter."""
+    keep, fp = _filter_ptr(filter)
+    key = np.ascontiguousarray(key, dtype=A.FLOW_KEY)
+    info = np.ascontiguousarray(info, dtype=A.FLOW_INFO)
+    rc = A.gpu_lib().dp_flow_filter_match(fp, key.ctypes.data, info.ctypes.data)
+    if rc not in (0, 1):
+        raise ValueError(f"invalid flow filter (rc={rc})")
+    return bool(rc)
+
+
 class FlowTable:
     """A device flow table (dp_flow_table_create)."""
 
@@ -70,6 +134,37 @@ class FlowTable:
         A.check(self.lib.dp_flow_table_create(device, slots, C.byref(h)), "dp_flow_table_create",
                 self.lib)
         self.h = h
+        self.slots = slots
+
+    def snapshot_page(self, filter=None, cursor: int = 0, cap: int = 1 << 16, device_ptr: int = 0):
+        """dp_flow_snapshot from slot `cursor`: (entries, next cursor, matched)
+        -- at most `cap` FLOW_ENTRY records in slot order, the cursor to go on
+        from (``self.slots``: the end was reached) and the matches from
+        `cursor` to the end.  With `device_ptr` (room for `cap` records in
+        device memory) the entries are written there
+        (dp_flow_snapshot_device) and their count is returned in their place."""
+        keep, fp = _filter_ptr(filter)
+        out = np.zeros(0 if device_ptr else cap, A.FLOW_ENTRY)
+        cur, n, matched = C.c_uint64(cursor), C.c_uint32(), C.c_uint64()
+        call = self.lib.dp_flow_snapshot_device if device_ptr else self.lib.dp_flow_snapshot
+        dst = device_ptr if device_ptr else (out.ctypes.data if cap else None)
+        A.check(call(self.h, fp, C.byref(cur), dst, cap, C.byref(n), C.byref(matched)),
+                "dp_flow_snapshot", self.lib)
+        return (n.value if device_ptr else out[:n.value]), cur.value, matched.value
+
+    def snapshot(self, filter=None, cap: Optional[int] = None) -> np.ndarray:
+        """FlowTable::snapshot(filter) (table.rs:355-372): every stored flow the
+        filter selects (None: all), paged `cap` entries a call.  Nothing else
+        may modify the table meanwhile."""
+        pages, cursor = [], 0
+        while cursor < self.slots:
+            page, cursor, _ = self.snapshot_page(filter, cursor, cap or 1 << 16)
+            pages.append(page)
+        return np.concatenate(pages) if pages else np.zeros(0, A.FLOW_ENTRY)
+
+    def count_matching(self, filter=None) -> int:
+        """The stored flows the filter selects (a count-only dp_flow_snapshot)."""
+        return self.snapshot_page(filter, 0, 0)[2]
 
     def set_capacity(self, capacity: int) -> None:
         A.check(self.lib.dp_flow_table_set_capacity(self.h, capacity), "set_capacity", self.lib)

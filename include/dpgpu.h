@@ -968,6 +968,111 @@ int dp_flow_count(dp_flow_table_t *ft, uint64_t *len, uint64_t *active);
  * must live on the context's device and outlive the attachment. */
 int dp_ctx_attach_flow_table(dp_ctx_t *ctx, dp_flow_table_t *ft);
 
+/* ------------------------------------------------------------------------ */
+/* Flow-table snapshot: FlowTable::for_each_flow_filtered / snapshot(filter) */
+/* (flow-entry/src/flow_table/table.rs:319-372) on the device.  A            */
+/* declarative filter selects stored flows; the selected flows are written,  */
+/* in ascending slot order, as dp_flow_entry_t records: the scan and the     */
+/* compaction run in HBM and only the matches cross the bus.  A cursor       */
+/* chunks a walk (the chunking table.rs:374-376 asks for).                   */
+/*                                                                           */
+/* Only stored flows are seen, whatever their FlowStatus (a Detached flow    */
+/* that a replacement or a remove took out of the table is not stored).      */
+/*                                                                           */
+/* Order.  For a given table state the order is deterministic (ascending     */
+/* slot), and it carries no meaning -- the reference's DashMap order has     */
+/* none either.  A walk over several calls is consistent only if nothing     */
+/* modifies the table in between (inserts, removes, sweeps, flows bursts);   */
+/* between the calls the table is free.                                      */
+/* ------------------------------------------------------------------------ */
+enum dp_flowf {
+    DP_FLOWF_SRC_VNI = 1u << 0,     /* key.src_vni == src_vni (0: None) */
+    DP_FLOWF_DST_VNI = 1u << 1,     /* info.dst_vni == dst_vni */
+    DP_FLOWF_FAMILY = 1u << 2,      /* key.family == family (4 / 6) */
+    DP_FLOWF_KIND = 1u << 3,        /* bit key.kind of kind_mask (enum dp_flow_kind) */
+    DP_FLOWF_SRC = 1u << 4,         /* key.src inside `src`; a prefix of the other family is false */
+    DP_FLOWF_DST = 1u << 5,         /* key.dst inside `dst` */
+    DP_FLOWF_SPORT = 1u << 6,       /* sport_lo <= key.sport <= sport_hi, whatever the kind (an ICMP */
+    DP_FLOWF_DPORT = 1u << 7,       /*   query's identifier sits in sport); likewise key.dport */
+    DP_FLOWF_STATUS = 1u << 8,      /* bit info.status of status_mask (enum dp_flow_status) */
+    DP_FLOWF_FLAGS_ALL = 1u << 9,   /* (info.flags & flags_all) == flags_all (enum dp_flow_flag) */
+    DP_FLOWF_FLAGS_NONE = 1u << 10, /* (info.flags & flags_none) == 0 */
+    DP_FLOWF_GENID_LT = 1u << 11,   /* info.genid < genid ("what is stale") */
+    DP_FLOWF_GENID_EQ = 1u << 12,   /* info.genid == genid */
+    DP_FLOWF_EXPIRES_LE = 1u << 13, /* info.expires_at <= expires_at */
+    DP_FLOWF_NAT = 1u << 14,        /* the flow is in a class of nat_mask (enum dp_flow_nat) */
+    DP_FLOWF_NAT_IP = 1u << 15,     /* use_ip (info.pf_ip / pf_family) of the flow's port-forwarding or */
+    DP_FLOWF_NAT_PORT = 1u << 16    /*   masquerade state inside nat_ip; use_port (info.pf_port) in
+                                         [nat_port_lo, nat_port_hi]; false for a flow with neither state */
+};
+/* NAT classes (not exclusive): info.pf != DP_PF_NONE; info.masq != DP_PF_NONE;
+ * info.masq != DP_PF_NONE with info.masq_alloc */
+enum dp_flow_nat { DP_FLOW_NAT_PF = 1, DP_FLOW_NAT_MASQ = 2, DP_FLOW_NAT_MASQ_ALLOC = 4 };
+
+/* Every set clause must hold; clauses == 0 selects every stored flow.  The
+ * fields of a clause that is not set are ignored.  A prefix's host bits are
+ * ignored.  112 bytes, no implicit padding. */
+typedef struct dp_flow_filter {
+    uint32_t clauses;            /* enum dp_flowf */
+    uint32_t src_vni, dst_vni;
+    uint8_t family;
+    uint8_t kind_mask;           /* 1 << kind */
+    uint8_t status_mask;         /* 1 << status */
+    uint8_t nat_mask;            /* enum dp_flow_nat */
+    uint32_t flags_all, flags_none;
+    uint16_t sport_lo, sport_hi, dport_lo, dport_hi;   /* inclusive */
+    uint16_t nat_port_lo, nat_port_hi;
+    dp_prefix_t src, dst, nat_ip;
+    int64_t genid;               /* GENID_LT and GENID_EQ share it */
+    uint64_t expires_at;
+} dp_flow_filter_t;              /* 112 B */
+
+/* One selected flow: its key, the slot it sits in (informational: the low
+ * half of info.ref) and its dp_flow_info_t exactly as dp_flow_lookup of that
+ * key fills it.  136 bytes, 8-byte aligned. */
+typedef struct dp_flow_entry {
+    dp_flow_key_t key;
+    uint32_t slot;
+    dp_flow_info_t info;
+} dp_flow_entry_t;               /* 136 B */
+#ifdef __cplusplus
+static_assert(sizeof(dp_flow_filter_t) == 112 && sizeof(dp_flow_entry_t) == 136, "snapshot ABI");
+#else
+_Static_assert(sizeof(dp_flow_filter_t) == 112 && sizeof(dp_flow_entry_t) == 136, "snapshot ABI");
+#endif
+
+/* The filter's predicate on the host, and its specification: 1 the flow
+ * (key, info) is selected, 0 it is not; needs no device.  `filter` NULL
+ * selects every flow.  DP_EINVAL: key or info NULL, an unknown clause, a set
+ * prefix clause whose family is not 4 / 6 or whose length exceeds it, a set
+ * range clause with lo > hi. */
+int dp_flow_filter_match(const dp_flow_filter_t *filter, const dp_flow_key_t *key,
+                         const dp_flow_info_t *info);
+
+/* The stored flows `filter` selects (NULL: all), scanning from slot `*cursor`
+ * (0 starts a walk; `cursor` NULL: from 0, nothing reported; above the slot
+ * count: DP_EINVAL).  `entries[0 .. *n_entries)` receive the first
+ * min(cap, matches from the cursor on) matches in ascending slot order --
+ * always an exact prefix.  On return `*cursor` is the slot after the last
+ * entry returned, or the slot count when the call reached the end (every
+ * match from the starting cursor on was returned): page by calling again
+ * until it equals the slot count (`slots` of dp_flow_table_create).  With
+ * cap 0 and matches left, `*cursor` is unchanged.  `matched` (may be NULL)
+ * receives the matches from the starting cursor to the end of the table,
+ * whatever `cap`; `entries` NULL with cap 0 is a count-only call
+ * (dp_flow_count generalised).  `n_entries` may be NULL.  Synchronous, in the
+ * table's order like the other management calls.  DP_EINVAL also for an
+ * invalid filter (dp_flow_filter_match) and for cap > 0 with `entries`
+ * NULL. */
+int dp_flow_snapshot(dp_flow_table_t *ft, const dp_flow_filter_t *filter, uint64_t *cursor,
+                     dp_flow_entry_t *entries, uint32_t cap, uint32_t *n_entries,
+                     uint64_t *matched);
+/* The same with `entries` in device memory (the table's device, 8-byte
+ * aligned); they are written when the call returns. */
+int dp_flow_snapshot_device(dp_flow_table_t *ft, const dp_flow_filter_t *filter, uint64_t *cursor,
+                            dp_flow_entry_t *dev_entries, uint32_t cap, uint32_t *n_entries,
+                            uint64_t *matched);
+
 
 /* ------------------------------------------------------------------------ */
 /* DPDK rx / tx burst glue: an rx burst of rte_mbufs  */

@@ -269,7 +269,8 @@ GPU_SYMBOLS = ["dp_abi_version", "dp_ctx_create", "dp_ctx_destroy", "dp_tables_p
                "dp_vpc_stats_accumulate_device", "dp_vpc_stats_read", "dp_fib_lookup",
                "dp_fib_lookup_device", "dp_capture_open", "dp_capture_set_filter",
                "dp_capture_close", "dp_capture_device", "dp_capture_read",
-               "dp_flow_filter_match", "dp_flow_snapshot", "dp_flow_snapshot_device"]
+               "dp_flow_filter_match", "dp_flow_snapshot", "dp_flow_snapshot_device",
+               "dp_tx_plan_device", "dp_tx_plan", "dp_mbuf_burst_tx"]
 # dp_acl_key_t / dp_acl_result_t (the ACL classifier alone)
 ACL_KEY = np.dtype([("src_vni", "<u4"), ("dst_vni", "<u4"), ("family", "u1"), ("proto", "u1"),
                     ("sport", "<u2"), ("dport", "<u2"), ("pad", "u1", 2), ("src", "u1", 16),
@@ -330,7 +331,12 @@ FLOWF = {n: 1 << i for i, n in enumerate(                                # enum 
     ["SRC_VNI", "DST_VNI", "FAMILY", "KIND", "SRC", "DST", "SPORT", "DPORT", "STATUS", "FLAGS_ALL",
      "FLAGS_NONE", "GENID_LT", "GENID_EQ", "EXPIRES_LE", "NAT", "NAT_IP", "NAT_PORT"])}
 FLOW_NAT_PF, FLOW_NAT_MASQ, FLOW_NAT_MASQ_ALLOC = 1, 2, 4                # enum dp_flow_nat
-NP_STRUCTS = dict(dp_flow_filter_t=FLOW_FILTER, dp_flow_entry_t=FLOW_ENTRY, dp_flow_key_t=FLOW_KEY, dp_flow_t=FLOW, dp_flow_info_t=FLOW_INFO, dp_acl_key_t=ACL_KEY,
+# TX plan (include/dpgpu.h "TX plan"): dp_tx_port_t, one per bucket of the plan
+TX_PORT = np.dtype([("oif", "<u4"), ("first", "<u4"), ("count", "<u4"), ("pad", "<u4"), ("bytes", "<u8")])
+assert TX_PORT.itemsize == 24
+TX_MAX_PORTS = 62     # DP_TX_MAX_PORTS
+TX_PLAN_TILE = 2048   # dpt::kTile (csrc/dp_txplan.h): packets a workgroup of the plan takes
+NP_STRUCTS = dict(dp_tx_port_t=TX_PORT, dp_flow_filter_t=FLOW_FILTER, dp_flow_entry_t=FLOW_ENTRY, dp_flow_key_t=FLOW_KEY, dp_flow_t=FLOW, dp_flow_info_t=FLOW_INFO, dp_acl_key_t=ACL_KEY,
                   dp_acl_result_t=ACL_RESULT, dp_ff_input_t=FF_INPUT, dp_ff_result_t=FF_RESULT,
                   dp_vpc_stat_t=VPC_STAT, dp_fib_key_t=FIB_KEY, dp_fib_result_t=FIB_RESULT,
                   dp_capture_filter_t=CAP_FILTER, dp_cap_rec_t=CAP_REC)
@@ -458,6 +464,9 @@ def gpu_lib() -> C.CDLL:
         lib.dp_flow_snapshot.argtypes = [_VP, _VP, C.POINTER(C.c_uint64), _VP, C.c_uint32,
                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         lib.dp_flow_snapshot_device.argtypes = lib.dp_flow_snapshot.argtypes
+        lib.dp_tx_plan_device.argtypes = [_VP, _VP, C.c_uint32, _VP, C.c_uint32, _VP, _VP, _VP]
+        lib.dp_tx_plan.argtypes = [_VP, _VP, C.c_uint32, _VP, C.c_uint32, _VP, _VP]
+        lib.dp_mbuf_burst_tx.argtypes = [_VP, C.c_uint32, _VP, C.c_uint32, _VP]
         lib.dpd_debug_set_fib_lookup_form.argtypes = [C.c_int]
         lib.dpd_debug_classify_copies.argtypes = [C.c_int]
         lib.dpd_debug_hip_runtimes.restype = C.c_int

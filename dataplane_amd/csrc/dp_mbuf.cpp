@@ -86,4 +86,15 @@ int dp_mbuf_burst_out(void *const *mbufs, uint32_t n, const dp_mbuf_layout_t *la
   return 0;
 }
 
+// The mbufs in TX-plan order: with dp_tx_port_t.first / .count, the array
+// TxQueue::transmit of each port takes (dpdk/src/queue/tx.rs:141-169).
+int dp_mbuf_burst_tx(void *const *mbufs, uint32_t n, const uint32_t *order, uint32_t n_order, void **tx_mbufs) {
+  if (n_order && (!mbufs || !order || !tx_mbufs)) return DP_EINVAL;
+  for (uint32_t k = 0; k < n_order; k++) {
+    if (order[k] >= n) return DP_EINVAL;
+    tx_mbufs[k] = mbufs[order[k]];
+  }
+  return 0;
+}
+
 }  // extern "C"

@@ -37,12 +37,15 @@
 #include "dp_tables.h"
 #include "dp_vpcstats.h"
 #include "dp_capture.h"
+#include "dp_txplan.h"
 
 extern "C" int dpk_capture(int tap, const uint8_t *buf, uint64_t buf_bytes, const void *recs,
                            const dp_pkt_meta_t *meta, uint32_t n, const dpc::Filter *f, void *scratch,
                            void *state, void *out_recs, void *out_bytes, uint32_t max_records,
                            uint64_t max_units, hipStream_t stream);
 extern "C" int dpk_capture_reset(void *state, hipStream_t stream);
+extern "C" hipError_t dpk_tx_plan(const dp_pkt_out_t *out, uint32_t n, const dpt::Ports *pl, void *scratch,
+                                  uint32_t *order, dp_tx_port_t *ports, hipStream_t stream);
 extern "C" int dpk_vpc_stats(const dp_pkt_out_t *out, const dp_pkt_meta_t *meta, uint32_t n, void *table,
                              uint32_t max_blocks, hipStream_t stream);
 extern "C" int dpk_launch_pipeline(const uint8_t *img_base, const void *image_dev, uint8_t *buf,
@@ -325,6 +328,13 @@ struct dp_ctx {
   uint64_t cp_scratch_cap = 0;
   hipEvent_t cp_used = nullptr;
   bool cp_armed = false;
+  // TX plan (dp_tx_plan_device): the launch scratch (bucket bytes and per-tile
+  // counts, byte sums and bases, grown on demand) and the event that orders
+  // one plan behind the last
+  void *tx_scratch = nullptr;
+  uint64_t tx_scratch_cap = 0;
+  hipEvent_t tx_used = nullptr;
+  bool tx_armed = false;
   // host threads of the staged-copy path, the context's own: a staged burst
   // waits for its own chunks only, never for another worker's
   std::unique_ptr<HostPool> pool;
@@ -618,6 +628,48 @@ void cp_free(dp_ctx *c) {
   c->cp_scratch = nullptr, c->cp_scratch_cap = 0, c->cp_armed = false, c->cp_open = false;
 }
 
+// The caller's TX port list as the plan's kernels take it; DP_EINVAL for a
+// list the contract refuses.
+int tx_lower(const uint32_t *oifs, uint32_t n_ports, dpt::Ports *out) {
+  if (n_ports > DP_TX_MAX_PORTS) return fail(DP_EINVAL, "TX plan: more than DP_TX_MAX_PORTS ports");
+  if (n_ports && !oifs) return fail(DP_EINVAL, "TX plan: null port list");
+  dpt::Ports p{};
+  p.n = n_ports;
+  for (uint32_t i = 0; i < n_ports; i++) {
+    if (oifs[i] == 0) return fail(DP_EINVAL, "TX plan: ifindex 0 in the port list");
+    for (uint32_t j = 0; j < i; j++)
+      if (oifs[j] == oifs[i]) return fail(DP_EINVAL, "TX plan: duplicate in the port list");
+    p.oif[i] = oifs[i];
+  }
+  *out = p;
+  return 0;
+}
+
+// One TX plan (the three kernels of dp_txplan.hip) over n > 0 records on `s`,
+// ordered behind the context's previous one: they share the scratch.
+int tx_launch(dp_ctx *c, const dp_pkt_out_t *dev_out, uint32_t n, const dpt::Ports &pl, uint32_t *dev_order,
+              dp_tx_port_t *dev_ports, hipStream_t s) {
+  if (!dev_out || !dev_order || !dev_ports) return fail(DP_EINVAL, "TX plan: null array");
+  if (((uintptr_t)dev_out & 15) || ((uintptr_t)dev_order & 3) || ((uintptr_t)dev_ports & 7))
+    return fail(DP_EINVAL, "TX plan: misaligned array");
+  if (!c->tx_used && hipEventCreateWithFlags(&c->tx_used, hipEventDisableTiming) != hipSuccess)
+    return fail(DP_ENOMEM, "TX plan event");
+  const uint64_t need = dpt::scratch_bytes(n);
+  if (need > c->tx_scratch_cap) {
+    if (c->tx_armed) (void)hipEventSynchronize(c->tx_used);
+    if (c->tx_scratch) (void)hipFree(c->tx_scratch);
+    c->tx_scratch = nullptr;
+    c->tx_scratch_cap = 0;
+    if (hipMalloc(&c->tx_scratch, need) != hipSuccess) return fail(DP_ENOMEM, "TX plan scratch");
+    c->tx_scratch_cap = need;
+  }
+  if (c->tx_armed && hipStreamWaitEvent(s, c->tx_used, 0) != hipSuccess) return fail(DP_EIO, "stream wait");
+  const hipError_t e = dpk_tx_plan(dev_out, n, &pl, c->tx_scratch, dev_order, dev_ports, s);
+  // (whatever was enqueued uses the scratch, also on a failure)
+  if (hipEventRecord(c->tx_used, s) == hipSuccess) c->tx_armed = true;
+  return e != hipSuccess ? fail(DP_EIO, "TX plan launch failed", e) : 0;
+}
+
 // The meta scratch of a statistics burst without a meta array, for n packets,
 // ordered on `s` behind the burst that used it last.
 dp_pkt_meta_t *vs_scratch(dp_ctx *c, uint32_t n, hipStream_t s) {
@@ -724,6 +776,8 @@ int dp_ctx_destroy(dp_ctx_t *c) {
   if (c->vs_host) (void)hipHostFree(c->vs_host);
   if (c->vs_meta) (void)hipFree(c->vs_meta);
   cp_free(c);
+  if (c->tx_used) { (void)hipEventSynchronize(c->tx_used); (void)hipEventDestroy(c->tx_used); }
+  if (c->tx_scratch) (void)hipFree(c->tx_scratch);
   if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
   if (c->side_fork) (void)hipEventDestroy(c->side_fork);
   if (c->side_fork2) (void)hipEventDestroy(c->side_fork2);
@@ -1096,26 +1150,35 @@ int dp_acl_classify_device(dp_ctx_t *c, const dp_acl_key_t *dev_keys, dp_acl_res
   return 0;
 }
 
+// Where a second result array starts behind a first of `bytes` bytes.
+static size_t cls_second(size_t bytes) { return (bytes + 7) & ~(size_t)7; }
+
 // A classifier over keys and results in host memory: the keys staged through
 // pinned memory onto the device, the lookups, the results back -- every copy
 // ordered on the context's stream, one synchronisation at the end.
 // `launch(dev_in, dev_out)` enqueues the lookups on the context's stream.
+// With `out2`, the launch leaves a second result array cls_second(out_bytes)
+// behind the first.
 static int classify_host(dp_ctx_t *c, const void *in, size_t in_bytes, void *out, size_t out_bytes,
-                         const std::function<int(const void *, void *)> &launch) {
+                         const std::function<int(const void *, void *)> &launch, void *out2 = nullptr,
+                         size_t out2_bytes = 0) {
   (void)hipSetDevice(c->device);
   hipError_t e;
-  const size_t in_al = (in_bytes + 255) & ~(size_t)255, need = in_al + out_bytes;
+  const size_t in_al = (in_bytes + 255) & ~(size_t)255, off2 = cls_second(out_bytes);
+  const size_t res_bytes = out2 ? off2 + out2_bytes : out_bytes, need = in_al + res_bytes;
   if (g_cls_copies.load(std::memory_order_relaxed) == 1) {
     // the round-5 path: stream-ordered allocations, asynchronous copies
     // to and from pageable memory
     void *d = nullptr;
     if ((e = hipMallocAsync(&d, need, c->stream)) != hipSuccess) return fail(DP_ENOMEM, "classify buffers", e);
+    uint8_t *dres = (uint8_t *)d + in_al;
     int rc = 0;
     if ((e = hipMemcpyAsync(d, in, in_bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
       rc = fail(DP_EIO, "classify keys copy", e);
-    if (!rc) rc = launch(d, (uint8_t *)d + in_al);
-    if (!rc && (e = hipMemcpyAsync(out, (uint8_t *)d + in_al, out_bytes, hipMemcpyDeviceToHost, c->stream)) !=
-                   hipSuccess)
+    if (!rc) rc = launch(d, dres);
+    if (!rc && ((e = hipMemcpyAsync(out, dres, out_bytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
+                (out2 && (e = hipMemcpyAsync(out2, dres + off2, out2_bytes, hipMemcpyDeviceToHost, c->stream)) !=
+                             hipSuccess)))
       rc = fail(DP_EIO, "classify results copy", e);
     (void)hipFreeAsync(d, c->stream);
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess && !rc) rc = fail(DP_EIO, "classify", e);
@@ -1142,11 +1205,12 @@ static int classify_host(dp_ctx_t *c, const void *in, size_t in_bytes, void *out
   if ((e = hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
     return fail(DP_EIO, "classify keys copy", e);
   int rc = launch(din, din + in_al);
-  if (!rc && (e = hipMemcpyAsync(hin + in_al, din + in_al, out_bytes, hipMemcpyDeviceToHost, c->stream)) !=
+  if (!rc && (e = hipMemcpyAsync(hin + in_al, din + in_al, res_bytes, hipMemcpyDeviceToHost, c->stream)) !=
                  hipSuccess)
     rc = fail(DP_EIO, "classify results copy", e);
   if ((e = hipStreamSynchronize(c->stream)) != hipSuccess && !rc) rc = fail(DP_EIO, "classify", e);
   if (!rc) std::memcpy(out, hin + in_al, out_bytes);
+  if (!rc && out2) std::memcpy(out2, hin + in_al + off2, out2_bytes);
   return rc;
 }
 
@@ -1968,6 +2032,48 @@ int dp_capture_read(dp_ctx_t *c, dp_cap_rec_t *recs, uint32_t rec_cap, uint8_t *
   if (reset && dpk_capture_reset(c->cp_state, s)) return fail(DP_EIO, "capture reset", hipGetLastError());
   if ((e = hipStreamSynchronize(s)) != hipSuccess) return fail(DP_EIO, "capture copy", e);
   return 0;
+}
+
+int dp_tx_plan_device(dp_ctx_t *c, const dp_pkt_out_t *dev_out, uint32_t n, const uint32_t *oifs, uint32_t n_ports,
+                      uint32_t *dev_order, dp_tx_port_t *dev_ports, void *stream) {
+  if (!c) return fail(DP_EINVAL, "null ctx");
+  dpt::Ports pl;
+  if (int rc = tx_lower(oifs, n_ports, &pl)) return rc;
+  if (n == 0) return 0;
+  (void)hipSetDevice(c->device);
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  reap(c);
+  if (int rc = tx_launch(c, dev_out, n, pl, dev_order, dev_ports, s)) return rc;
+  // dp_ctx_synchronize waits for it like for a burst
+  InFlight f;
+  f.done = take_event(c);
+  if (f.done) (void)hipEventRecord(f.done, s);
+  c->inflight.push_back(std::move(f));
+  return 0;
+}
+
+// The plan over host memory, staged like a classifier's keys and results:
+// the records in, order and ports (8-byte aligned behind it) back.
+int dp_tx_plan(dp_ctx_t *c, const dp_pkt_out_t *out, uint32_t n, const uint32_t *oifs, uint32_t n_ports,
+               uint32_t *order, dp_tx_port_t *ports) {
+  if (!c) return fail(DP_EINVAL, "null ctx");
+  dpt::Ports pl;
+  if (int rc = tx_lower(oifs, n_ports, &pl)) return rc;
+  if (n == 0) {
+    for (uint32_t b = 0; ports && b < n_ports + 2; b++) ports[b] = dp_tx_port_t{b < n_ports ? oifs[b] : 0u, 0, 0, 0, 0};
+    return 0;
+  }
+  if (!out || !order || !ports) return fail(DP_EINVAL, "TX plan: null array");
+  const size_t ord_bytes = sizeof(uint32_t) * (size_t)n;
+  return classify_host(
+      c, out, sizeof(dp_pkt_out_t) * (size_t)n, order, ord_bytes,
+      [&](const void *d_out, void *d_order) {
+        reap(c);
+        return tx_launch(c, static_cast<const dp_pkt_out_t *>(d_out), n, pl, static_cast<uint32_t *>(d_order),
+                         reinterpret_cast<dp_tx_port_t *>(static_cast<uint8_t *>(d_order) + cls_second(ord_bytes)),
+                         c->stream);
+      },
+      ports, sizeof(dp_tx_port_t) * (n_ports + 2));
 }
 
 int dp_ctx_synchronize(dp_ctx_t *c) {

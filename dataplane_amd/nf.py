@@ -337,6 +337,29 @@ class GpuPathNf:
     def capture_close(self) -> None:
         A.check(self.lib.dp_capture_close(self.ctx), "dp_capture_close", self.lib)
 
+    # -- TX plan (what the drivers do after pipeline.process: worker.rs:239-251, tx.rs:141-169) --
+    def tx_plan(self, out: np.ndarray, oifs):
+        """dp_tx_plan over A.PKT_OUT records in host memory: (order, ports) --
+        the packet indexes grouped by TX port in the order of `oifs`, then the
+        Delivered packets without a port of the list, then the packets to
+        free; one A.TX_PORT record per bucket (len(oifs) + 2)."""
+        out = np.ascontiguousarray(out, dtype=A.PKT_OUT)
+        oifs = np.ascontiguousarray(oifs, dtype=np.uint32).reshape(-1)
+        order = np.zeros(len(out), dtype=np.uint32)
+        ports = np.zeros(len(oifs) + 2, dtype=A.TX_PORT)
+        A.check(self.lib.dp_tx_plan(self.ctx, out.ctypes.data, len(out), oifs.ctypes.data, len(oifs),
+                                    order.ctypes.data, ports.ctypes.data), "dp_tx_plan", self.lib)
+        return order, ports
+
+    def tx_plan_device(self, dev_out: int, n: int, oifs, dev_order: int, dev_ports: int,
+                       stream: Optional[int] = None) -> None:
+        """The plan over n device-resident dp_pkt_out_t records (dp_tx_plan_device):
+        raw device pointers (dev_order: n u32, dev_ports: len(oifs) + 2
+        A.TX_PORT records), asynchronous on `stream`; `oifs` is host memory."""
+        oifs = np.ascontiguousarray(oifs, dtype=np.uint32).reshape(-1)
+        A.check(self.lib.dp_tx_plan_device(self.ctx, dev_out, n, oifs.ctypes.data, len(oifs), dev_order,
+                                           dev_ports, stream), "dp_tx_plan_device", self.lib)
+
     def close(self) -> None:
         if self.ctx:
             self.lib.dp_ctx_destroy(self.ctx)

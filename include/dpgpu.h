@@ -1287,6 +1287,57 @@ int dp_capture_device(dp_ctx_t *, int tap, const uint8_t *dev_buf, uint64_t buf_
 int dp_capture_read(dp_ctx_t *, dp_cap_rec_t *recs, uint32_t rec_cap, uint8_t *bytes, uint64_t byte_cap,
                     uint32_t *n_recs, uint64_t *n_bytes, uint64_t *matched, uint64_t *lost, int reset);
 
+/* ------------------------------------------------------------------------ */
+/* TX plan: what the reference's drivers do with a burst after               */
+/* pipeline.process(burst), on the device.  The kernel driver transmits each */
+/* Delivered packet on the interface meta.oif names and counts a missing or  */
+/* unknown oif as a TX drop (dataplane/src/drivers/kernel/worker.rs:239-251, */
+/* tx_packet :549-575); TxQueue::transmit takes the packets of ONE port as   */
+/* an array (dpdk/src/queue/tx.rs:141-169).  A TX plan of n out records over */
+/* a caller-given list of TX ports oifs[n_ports] is a stable partition of    */
+/* the packet indexes 0..n-1 into n_ports + 2 buckets:                       */
+/*   bucket b < n_ports: out[i].done == DP_DONE_DELIVERED and                */
+/*     out[i].oif == oifs[b] -- the packets TxQueue::transmit of that port   */
+/*     gets; the buckets follow the list's order, not the ifindexes';        */
+/*   bucket n_ports: Delivered, but oif is 0 (None) or not in the list: the  */
+/*     reference's TX drop;                                                  */
+/*   bucket n_ports + 1: every other done value (DP_DONE_NONE and values     */
+/*     >= DP_DONE_COUNT included): the packets the caller frees.             */
+/* Within a bucket the indexes ascend: a flow's packets leave a port in the  */
+/* order they arrived.                                                       */
+/* order[n] receives the indexes, bucket after bucket; ports[n_ports + 2] a  */
+/* dp_tx_port_t per bucket: oif (0 for the two special buckets), first (into */
+/* order), count, bytes (the sum of out.len over the bucket);                */
+/* ports[b].first + ports[b].count == ports[b + 1].first, and the last       */
+/* bucket ends at n.                                                         */
+/* oifs is host memory, read during the call and never retained.  DP_EINVAL: */
+/* n_ports > DP_TX_MAX_PORTS, a 0 or a duplicate in oifs, a NULL array with  */
+/* n > 0, out not 16-byte aligned, order / ports not 4- / 8-byte aligned     */
+/* (device form).  n = 0 is DP_OK: the host form fills ports with zero       */
+/* counts, the device form launches and writes nothing.  No published tables */
+/* are needed.  Plans of one context run one after the other, whatever their */
+/* streams (they share the context's launch scratch).                        */
+/* ------------------------------------------------------------------------ */
+#define DP_TX_MAX_PORTS 62u          /* + 2 special buckets = 64: one wave lane a bucket;
+                                        RTE_MAX_ETHPORTS is 32 */
+typedef struct dp_tx_port {
+    uint32_t oif, first, count, pad;
+    uint64_t bytes;
+} dp_tx_port_t;                      /* 24 B */
+
+/* Everything but oifs in device memory; enqueued on `stream` as
+ * dp_process_burst_device does; asynchronous. */
+int dp_tx_plan_device(dp_ctx_t *, const dp_pkt_out_t *dev_out, uint32_t n, const uint32_t *oifs,
+                      uint32_t n_ports, uint32_t *dev_order, dp_tx_port_t *dev_ports, void *stream);
+/* The same for records, order and ports in host memory; synchronous. */
+int dp_tx_plan(dp_ctx_t *, const dp_pkt_out_t *out, uint32_t n, const uint32_t *oifs, uint32_t n_ports,
+               uint32_t *order, dp_tx_port_t *ports);
+/* Host only, no device: tx_mbufs[k] = mbufs[order[k]] for k < n_order -- with
+ * ports[b].first / .count, the arrays rte_eth_tx_burst takes, after
+ * dp_mbuf_burst_out.  DP_EINVAL for an order[k] >= n (nothing is promised
+ * about tx_mbufs then) or a NULL array with n_order > 0. */
+int dp_mbuf_burst_tx(void *const *mbufs, uint32_t n, const uint32_t *order, uint32_t n_order, void **tx_mbufs);
+
 /* Introspection: bytes of the device table image and its parts (for
  * DESIGN.md / bench), and the last HIP error string. */
 uint64_t dp_tables_device_bytes(const dp_ctx_t *ctx);

@@ -270,7 +270,7 @@ GPU_SYMBOLS = ["dp_abi_version", "dp_ctx_create", "dp_ctx_destroy", "dp_tables_p
                "dp_fib_lookup_device", "dp_capture_open", "dp_capture_set_filter",
                "dp_capture_close", "dp_capture_device", "dp_capture_read",
                "dp_flow_filter_match", "dp_flow_snapshot", "dp_flow_snapshot_device",
-               "dp_tx_plan_device", "dp_tx_plan", "dp_mbuf_burst_tx"]
+               "dp_tx_plan_device", "dp_tx_plan", "dp_mbuf_burst_tx", "dp_tables_publish_stats"]
 # dp_acl_key_t / dp_acl_result_t (the ACL classifier alone)
 ACL_KEY = np.dtype([("src_vni", "<u4"), ("dst_vni", "<u4"), ("family", "u1"), ("proto", "u1"),
                     ("sport", "<u2"), ("dport", "<u2"), ("pad", "u1", 2), ("src", "u1", 16),
@@ -336,7 +336,14 @@ TX_PORT = np.dtype([("oif", "<u4"), ("first", "<u4"), ("count", "<u4"), ("pad", 
 assert TX_PORT.itemsize == 24
 TX_MAX_PORTS = 62     # DP_TX_MAX_PORTS
 TX_PLAN_TILE = 2048   # dpt::kTile (csrc/dp_txplan.h): packets a workgroup of the plan takes
-NP_STRUCTS = dict(dp_tx_port_t=TX_PORT, dp_flow_filter_t=FLOW_FILTER, dp_flow_entry_t=FLOW_ENTRY, dp_flow_key_t=FLOW_KEY, dp_flow_t=FLOW, dp_flow_info_t=FLOW_INFO, dp_acl_key_t=ACL_KEY,
+# publish statistics (include/dpgpu.h "Publish statistics"): dp_publish_stats_t
+PUBLISH_STATS = np.dtype([("device_fibs", "<u4"), ("pad", "<u4"), ("image_bytes", "<u8"), ("upload_bytes", "<u8"),
+                          ("built_bytes", "<u8"), ("sort_us", "<u8"), ("paint_us", "<u8"), ("compile_us", "<u8"),
+                          ("upload_us", "<u8"), ("kernel_ns", "<u8"), ("total_us", "<u8")])
+assert PUBLISH_STATS.itemsize == 80
+FIB_BUILD_TILE = 1024   # dpb::kTile (csrc/dp_fibbuild.h): /24 slots a workgroup of the device FIB build paints
+FIB_BUILD_STAGE = 1024  # dpb::kStage: routes starting in a tile that it stages in LDS (more are read from HBM)
+NP_STRUCTS = dict(dp_publish_stats_t=PUBLISH_STATS, dp_tx_port_t=TX_PORT, dp_flow_filter_t=FLOW_FILTER, dp_flow_entry_t=FLOW_ENTRY, dp_flow_key_t=FLOW_KEY, dp_flow_t=FLOW, dp_flow_info_t=FLOW_INFO, dp_acl_key_t=ACL_KEY,
                   dp_acl_result_t=ACL_RESULT, dp_ff_input_t=FF_INPUT, dp_ff_result_t=FF_RESULT,
                   dp_vpc_stat_t=VPC_STAT, dp_fib_key_t=FIB_KEY, dp_fib_result_t=FIB_RESULT,
                   dp_capture_filter_t=CAP_FILTER, dp_cap_rec_t=CAP_REC)
@@ -356,6 +363,7 @@ OPT_HOST_PATH = 1
 OPT_CLOCK = 2
 OPT_VPC_STATS = 3
 OPT_CAPTURE = 4
+OPT_DEVICE_FIB = 5
 HOST_AUTO, HOST_COPY, HOST_ZERO_COPY = 0, 1, 2
 
 _VP = C.c_void_p
@@ -467,6 +475,7 @@ def gpu_lib() -> C.CDLL:
         lib.dp_tx_plan_device.argtypes = [_VP, _VP, C.c_uint32, _VP, C.c_uint32, _VP, _VP, _VP]
         lib.dp_tx_plan.argtypes = [_VP, _VP, C.c_uint32, _VP, C.c_uint32, _VP, _VP]
         lib.dp_mbuf_burst_tx.argtypes = [_VP, C.c_uint32, _VP, C.c_uint32, _VP]
+        lib.dp_tables_publish_stats.argtypes = [_VP, _VP]
         lib.dpd_debug_set_fib_lookup_form.argtypes = [C.c_int]
         lib.dpd_debug_classify_copies.argtypes = [C.c_int]
         lib.dpd_debug_hip_runtimes.restype = C.c_int

@@ -46,6 +46,7 @@ extern "C" int dpk_capture(int tap, const uint8_t *buf, uint64_t buf_bytes, cons
 extern "C" int dpk_capture_reset(void *state, hipStream_t stream);
 extern "C" hipError_t dpk_tx_plan(const dp_pkt_out_t *out, uint32_t n, const dpt::Ports *pl, void *scratch,
                                   uint32_t *order, dp_tx_port_t *ports, hipStream_t stream);
+extern "C" hipError_t dpk_fib_build(const dpb::Job *job, hipStream_t stream);
 extern "C" int dpk_vpc_stats(const dp_pkt_out_t *out, const dp_pkt_meta_t *meta, uint32_t n, void *table,
                              uint32_t max_blocks, hipStream_t stream);
 extern "C" int dpk_launch_pipeline(const uint8_t *img_base, const void *image_dev, uint8_t *buf,
@@ -335,6 +336,14 @@ struct dp_ctx {
   uint64_t tx_scratch_cap = 0;
   hipEvent_t tx_used = nullptr;
   bool tx_armed = false;
+  // publish: DP_OPT_DEVICE_FIB, the build kernels' stream and timing events
+  // (created at the first device build), and the last successful publish's
+  // record (dp_tables_publish_stats)
+  bool device_fib = false;
+  hipStream_t fb_stream = nullptr;
+  hipEvent_t fb_t0 = nullptr, fb_t1 = nullptr;
+  dp_publish_stats_t pub_stats{};
+  bool pub_valid = false;
   // host threads of the staged-copy path, the context's own: a staged burst
   // waits for its own chunks only, never for another worker's
   std::unique_ptr<HostPool> pool;
@@ -778,6 +787,9 @@ int dp_ctx_destroy(dp_ctx_t *c) {
   cp_free(c);
   if (c->tx_used) { (void)hipEventSynchronize(c->tx_used); (void)hipEventDestroy(c->tx_used); }
   if (c->tx_scratch) (void)hipFree(c->tx_scratch);
+  if (c->fb_stream) (void)hipStreamDestroy(c->fb_stream);  // (idle: a publish waits for its build)
+  if (c->fb_t0) (void)hipEventDestroy(c->fb_t0);
+  if (c->fb_t1) (void)hipEventDestroy(c->fb_t1);
   if (c->side) { (void)hipStreamSynchronize(c->side); (void)hipStreamDestroy(c->side); }
   if (c->side_fork) (void)hipEventDestroy(c->side_fork);
   if (c->side_fork2) (void)hipEventDestroy(c->side_fork2);
@@ -791,8 +803,77 @@ int dp_ctx_destroy(dp_ctx_t *c) {
   return 0;
 }
 
+// The device build of a publish (DP_OPT_DEVICE_FIB): the build lists of every
+// such FIB go into one temporary device buffer, the kernels of dp_fibbuild.hip
+// fill the image's holes on the context's build stream, and the call waits for
+// them.  The buffer is freed on every path.
+static int fib_device_build(dp_ctx *c, uint8_t *img, const dpd::BuiltImage &bi, dp_publish_stats_t &st) {
+  hipError_t e;
+  if (!c->fb_stream && ((e = hipStreamCreateWithFlags(&c->fb_stream, hipStreamNonBlocking)) != hipSuccess ||
+                        (e = hipEventCreate(&c->fb_t0)) != hipSuccess || (e = hipEventCreate(&c->fb_t1)) != hipSuccess))
+    return fail(DP_ENOMEM, "device FIB build: stream / events", e);
+  auto al = [](uint64_t n) { return (n + 255) & ~(uint64_t)255; };
+  uint64_t need = 0;
+  for (const dpd::FibBuild &fb : bi.fib_builds) {
+    for (const dpb::Block &b : fb.blocks)
+      if (b.count > dpb::kBlockRoutes || (uint64_t)b.first + b.count > fb.longs.size() || b.slot >= dpb::kSlots)
+        return fail(DP_EINVAL, "device FIB build: bad block list");
+    if (fb.shorts.empty() || fb.direct + 4ull * dpb::kSlots > bi.im.bytes ||
+        fb.block16 + 512ull * fb.blocks.size() > bi.im.bytes)
+      return fail(DP_EINVAL, "device FIB build: bad regions");
+    need += al(sizeof(dpb::Short) * fb.shorts.size()) + al(sizeof(dpb::Block) * fb.blocks.size()) +
+            al(sizeof(dpb::Long) * fb.longs.size());
+  }
+  const auto t_lists = std::chrono::steady_clock::now();
+  uint8_t *lists = nullptr;
+  if ((e = hipMalloc(&lists, need)) != hipSuccess) return fail(DP_ENOMEM, "device FIB build: lists", e);
+  int rc = 0;
+  uint64_t o = 0;
+  std::vector<dpb::Job> jobs;
+  for (const dpd::FibBuild &fb : bi.fib_builds) {
+    dpb::Job j{};
+    auto put = [&](const void *p, uint64_t n) -> uint8_t * {
+      uint8_t *d = lists + o;
+      if (!rc && n && (e = hipMemcpy(d, p, n, hipMemcpyHostToDevice)) != hipSuccess)
+        rc = fail(DP_EIO, "device FIB build: upload lists", e);
+      o += al(n);
+      st.upload_bytes += n;
+      return d;
+    };
+    j.shorts = reinterpret_cast<const dpb::Short *>(put(fb.shorts.data(), sizeof(dpb::Short) * fb.shorts.size()));
+    j.blocks = reinterpret_cast<const dpb::Block *>(put(fb.blocks.data(), sizeof(dpb::Block) * fb.blocks.size()));
+    j.longs = reinterpret_cast<const dpb::Long *>(put(fb.longs.data(), sizeof(dpb::Long) * fb.longs.size()));
+    j.direct = reinterpret_cast<uint32_t *>(img + fb.direct);
+    j.block16 = reinterpret_cast<uint16_t *>(img + fb.block16);
+    j.n_short = (uint32_t)fb.shorts.size();
+    j.n_blocks = (uint32_t)fb.blocks.size();
+    jobs.push_back(j);
+    st.built_bytes += 4ull * dpb::kSlots + 512ull * fb.blocks.size();
+  }
+  st.upload_us += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_lists).count();
+  if (!rc) {
+    e = hipEventRecord(c->fb_t0, c->fb_stream);
+    for (size_t k = 0; k < jobs.size() && e == hipSuccess; k++) e = dpk_fib_build(&jobs[k], c->fb_stream);
+    if (e == hipSuccess) e = hipEventRecord(c->fb_t1, c->fb_stream);
+    // whatever was enqueued reads the lists: wait before they go
+    const hipError_t es = hipStreamSynchronize(c->fb_stream);
+    if (e == hipSuccess) e = es;
+    float ms = 0;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->fb_t0, c->fb_t1);
+    if (e != hipSuccess) rc = fail(DP_EIO, "device FIB build: kernels", e);
+    st.kernel_ns = (uint64_t)((double)ms * 1e6);
+  }
+  (void)hipFree(lists);
+  st.device_fibs = (uint32_t)jobs.size();
+  return rc;
+}
+
 int dp_tables_publish(dp_ctx_t *c, const dp_tables_desc_t *tables) {
   if (!c || !tables) return fail(DP_EINVAL, "null argument");
+  const auto t_in = std::chrono::steady_clock::now();
+  auto us_since = [](std::chrono::steady_clock::time_point t) {
+    return (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t).count();
+  };
   dpd::BuiltImage bi;
   DeviceTables &dt = dev_tables(c->device);
   std::lock_guard<std::mutex> publishing(dt.pub_mu);
@@ -801,21 +882,45 @@ int dp_tables_publish(dp_ctx_t *c, const dp_tables_desc_t *tables) {
     std::lock_guard<std::mutex> lk(dt.mu);
     pf = dt.pf;
   }
-  int rc = dpd::build_image(tables, bi, &pf);
+  int rc = dpd::build_image(tables, bi, &pf, c->device_fib);
   if (rc) return fail(rc, "table compile rejected the descriptors");
+  dp_publish_stats_t st{};
+  st.sort_us = bi.sort_us;
+  st.paint_us = bi.paint_us;
+  st.compile_us = us_since(t_in) - std::min(us_since(t_in), bi.sort_us + bi.paint_us);
+  const auto t_up = std::chrono::steady_clock::now();
   (void)hipSetDevice(c->device);
   drain_graveyard(c->device);  // images no burst reads any more
   auto img = std::make_shared<DevImage>();
   img->device = c->device;
   // the kernel reads the Image descriptor from HBM (scalar loads where used)
   // instead of taking it by value: 100+ kernel-argument SGPRs would spill
-  img->im_off = (bi.bytes.size() + 63) & ~(uint64_t)63;
-  bi.bytes.resize(img->im_off + sizeof(dpd::Image));
-  memcpy(bi.bytes.data() + img->im_off, &bi.im, sizeof(dpd::Image));
-  hipError_t e = hipMalloc(&img->dev, bi.bytes.size());
+  img->im_off = (bi.im.bytes + 63) & ~(uint64_t)63;
+  st.image_bytes = img->im_off + sizeof(dpd::Image);
+  hipError_t e = hipMalloc(&img->dev, st.image_bytes);
   if (e != hipSuccess) return fail(DP_ENOMEM, "hipMalloc table image", e);
-  if ((e = hipMemcpy(img->dev, bi.bytes.data(), bi.bytes.size(), hipMemcpyHostToDevice)) != hipSuccess)
-    return fail(DP_EIO, "upload table image", e);
+  // the image's bytes in pieces around its holes (none unless the device
+  // builds FIB tables), then the zero padding and the descriptor behind them
+  uint64_t off = 0, src = 0;
+  auto piece = [&](uint64_t end) {
+    const uint64_t n = end - off;
+    if (n && e == hipSuccess) e = hipMemcpy(img->dev + off, bi.bytes.data() + src, n, hipMemcpyHostToDevice);
+    src += n;
+    st.upload_bytes += n;
+  };
+  for (const dpd::ImageHole &h : bi.holes) {
+    piece(h.off);
+    off = h.off + h.bytes;
+  }
+  piece(bi.im.bytes);
+  std::vector<uint8_t> tail(st.image_bytes - bi.im.bytes, 0);
+  memcpy(tail.data() + (img->im_off - bi.im.bytes), &bi.im, sizeof(dpd::Image));
+  if (e == hipSuccess) e = hipMemcpy(img->dev + bi.im.bytes, tail.data(), tail.size(), hipMemcpyHostToDevice);
+  st.upload_bytes += tail.size();
+  if (e != hipSuccess) return fail(DP_EIO, "upload table image", e);
+  st.upload_us = us_since(t_up);
+  // the device-built tables, complete before any burst can see the image
+  if (!bi.fib_builds.empty() && (rc = fib_device_build(c, img->dev, bi, st)) != 0) return rc;
   img->im = bi.im;
   img->masq = bi.masq;
   img->serial = g_serial++;
@@ -826,6 +931,9 @@ int dp_tables_publish(dp_ctx_t *c, const dp_tables_desc_t *tables) {
     dt.cur = img;
     dt.pf = std::move(pf);
   }
+  st.total_us = us_since(t_in);
+  c->pub_stats = st;
+  c->pub_valid = true;
   // the attached flow tables' allocators follow the new config now (a table
   // attached later syncs at its first burst).  Every table is tried; the first
   // failure is returned, with the new image already published: a table that
@@ -842,6 +950,13 @@ int dp_tables_publish(dp_ctx_t *c, const dp_tables_desc_t *tables) {
     if (first) return fail(first, "masquerade allocator update (the new tables are published)");
   }
   // `old` is retired here only if no in-flight burst still references it
+  return 0;
+}
+
+int dp_tables_publish_stats(const dp_ctx_t *c, dp_publish_stats_t *out) {
+  if (!c || !out) return fail(DP_EINVAL, "null argument");
+  if (!c->pub_valid) return fail(DP_ENOTABLES, "no publish through this context yet");
+  *out = c->pub_stats;
   return 0;
 }
 
@@ -1496,6 +1611,11 @@ int dp_ctx_set_option(dp_ctx_t *c, int option, int64_t value) {
   if (option == DP_OPT_CAPTURE) {
     if (value & ~(int64_t)(DP_CAP_RX | DP_CAP_TX)) return fail(DP_EINVAL, "capture: a mask of DP_CAP_RX / DP_CAP_TX");
     c->cp_taps = (int)value;
+    return 0;
+  }
+  if (option == DP_OPT_DEVICE_FIB) {
+    if (value != 0 && value != 1) return fail(DP_EINVAL, "device FIB build: 0 or 1");
+    c->device_fib = value != 0;
     return 0;
   }
   return fail(DP_EINVAL, "unknown option");

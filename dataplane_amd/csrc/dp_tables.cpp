@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <cstddef>
@@ -40,18 +41,45 @@ namespace {
 
 typedef unsigned __int128 u128;
 
+// The image under construction.  Offsets are image offsets; `b` holds the
+// image's bytes without its holes -- regions reserved for the device to build
+// (BuiltImage::holes), which the host never materialises.
 struct ImgBuf {
   std::vector<uint8_t> b;
+  std::vector<ImageHole> holes;
+  uint64_t skipped = 0;  // bytes of the holes
+  uint64_t size() const { return b.size() + skipped; }
   uint64_t alloc(uint64_t n, uint64_t align = 16) {
-    uint64_t o = (b.size() + align - 1) & ~(align - 1);
-    b.resize(o + (n ? n : align), 0);
+    uint64_t o = (size() + align - 1) & ~(align - 1);
+    b.resize(o - skipped + (n ? n : align), 0);
     return o;
+  }
+  uint64_t reserve(uint64_t n, uint64_t align = 16) {
+    uint64_t o = (size() + align - 1) & ~(align - 1);
+    b.resize(o - skipped, 0);
+    holes.push_back(ImageHole{o, n});
+    skipped += n;
+    return o;
+  }
+  // the host bytes of image offset `off` (outside the holes)
+  uint8_t *at(uint64_t off) {
+    uint64_t before = 0;
+    for (const ImageHole &h : holes)
+      if (h.off < off) before += h.bytes;
+    return b.data() + (off - before);
   }
   template <class T> uint64_t put(const std::vector<T> &v, uint64_t align = 16) {
     uint64_t o = alloc(sizeof(T) * v.size(), alignof(T) > align ? alignof(T) : align);
-    if (!v.empty()) memcpy(b.data() + o, v.data(), sizeof(T) * v.size());
+    if (!v.empty()) memcpy(at(o), v.data(), sizeof(T) * v.size());
     return o;
   }
+};
+
+// What build_lpm reports besides the Lpm: the device build lists (null: every
+// table is host-built) and the time spent sorting / preparing and painting.
+struct LpmAux {
+  std::vector<FibBuild> *dev = nullptr;
+  std::chrono::steady_clock::duration sort{}, paint{};
 };
 
 inline uint32_t be32(const uint8_t *p) {
@@ -237,8 +265,40 @@ void add_v6_window(ImgBuf &ib, PtBuilder &pb, const std::vector<PRoute> &uniq, L
   L.wbits = (uint32_t)c;
 }
 
+// DIR-24-8 in device form (DP_OPT_DEVICE_FIB): the direct table and the blocks
+// are reserved at the offsets build_lpm puts them at and left to the kernels
+// of dp_fibbuild.hip; one pass over the sorted unique routes writes their lists.
+// The order is a pre-order of the prefix tree, so a stack of the short routes
+// that enclose the current one gives each its parent.
+Lpm reserve_dir248(ImgBuf &ib, const std::vector<PRoute> &uniq, FibBuild &fb) {
+  std::vector<uint32_t> stack;
+  for (const PRoute &r : uniq) {
+    const uint32_t s = kbits(r.key, 0, 24);
+    if (r.len <= 24) {
+      while (!stack.empty() && !dpb::covers(fb.shorts[stack.back()].slot, fb.shorts[stack.back()].len, s)) stack.pop_back();
+      const uint32_t me = (uint32_t)fb.shorts.size();
+      fb.shorts.push_back(dpb::Short{s, (uint32_t)r.len, r.nh, stack.empty() ? me : stack.back()});
+      stack.push_back(me);
+      continue;
+    }
+    if (fb.blocks.empty() || fb.blocks.back().slot != s) fb.blocks.push_back(dpb::Block{s, (uint32_t)fb.longs.size(), 0, 0});
+    fb.blocks.back().count++;
+    fb.longs.push_back(kbits(r.key, 24, 8) | (uint32_t)r.len << 8 | r.nh << 16);
+  }
+  Lpm L{};
+  if (fb.blocks.empty()) L.blocks = ib.put(std::vector<uint16_t>(256, 0));
+  else L.blocks = ib.reserve(512 * (uint64_t)fb.blocks.size());
+  L.direct = ib.reserve(4ull << 24);
+  L.dbits = 24;
+  L.width = 32;
+  fb.direct = L.direct;
+  fb.block16 = L.blocks;
+  return L;
+}
+
 // Build one FIB/family LPM; routes must include a /0.
-Lpm build_lpm(ImgBuf &ib, PtBuilder &pb, std::vector<PRoute> &routes, int width, uint32_t dbits, int v6wtb = 0) {
+Lpm build_lpm(ImgBuf &ib, PtBuilder &pb, std::vector<PRoute> &routes, int width, uint32_t dbits, LpmAux &aux, int v6wtb = 0) {
+  const auto t0 = std::chrono::steady_clock::now();
   // sort by (key, len), keep the last insert of a duplicate prefix
   std::stable_sort(routes.begin(), routes.end(), [](const PRoute &a, const PRoute &b) {
     if (a.key != b.key) return a.key < b.key;
@@ -251,6 +311,26 @@ Lpm build_lpm(ImgBuf &ib, PtBuilder &pb, std::vector<PRoute> &routes, int width,
     else
       uniq.push_back(routes[i]);
   }
+#if !defined(DP_DIR16) && !defined(DP_NO_DIR248)
+  if (aux.dev && width == 32 && dbits == 24) {
+    uint32_t top_nh = 0;
+    for (auto &r : uniq) top_nh = std::max(top_nh, r.nh);
+    if (top_nh < 0xffffu) {  // (the DIR-24-8 test below)
+      aux.dev->emplace_back();
+      const Lpm L = reserve_dir248(ib, uniq, aux.dev->back());
+      aux.sort += std::chrono::steady_clock::now() - t0;
+      return L;
+    }
+  }
+#endif
+  const auto t1 = std::chrono::steady_clock::now();
+  aux.sort += t1 - t0;
+  // (timed as "painting": the host build of the tables, from here to the return)
+  struct Painted {
+    LpmAux &aux;
+    std::chrono::steady_clock::time_point from;
+    ~Painted() { aux.paint += std::chrono::steady_clock::now() - from; }
+  } painted{aux, t1};
   std::vector<uint32_t> direct((size_t)1 << dbits, 0);
   std::vector<uint32_t> dval((size_t)1 << dbits, 0);
   // paint short routes in increasing length
@@ -800,18 +880,21 @@ void be_words(const dp_prefix_t &p, uint32_t w[4]) {
 
 }  // namespace
 
-int build_image(const dp_tables_desc_t *d, BuiltImage &out, PfLineage *pf) {
+int build_image(const dp_tables_desc_t *d, BuiltImage &out, PfLineage *pf, bool device_fib) {
+  LpmAux aux;
+  std::vector<FibBuild> fib_builds;
+  if (device_fib) aux.dev = &fib_builds;
   g_forms[0] = g_forms[1] = 0;
   g_group_stats.clear();
   if (!d || d->abi_version != DPGPU_ABI_VERSION) return DP_EINVAL;
   ImgBuf ib;
   ib.alloc(64);  // offset 0 is never a valid structure
   g_sections.clear();
-  uint64_t sec0 = ib.b.size();
+  uint64_t sec0 = ib.size();
   auto section = [&](const char *name) {
     g_sections += name;
-    g_sections += "=" + std::to_string(ib.b.size() - sec0) + " ";
-    sec0 = ib.b.size();
+    g_sections += "=" + std::to_string(ib.size() - sec0) + " ";
+    sec0 = ib.size();
   };
   Image im{};
   im.genid = d->genid;
@@ -959,8 +1042,8 @@ int build_image(const dp_tables_desc_t *d, BuiltImage &out, PfLineage *pf) {
     else
       for (const PRoute &p : r4[f])
         if (p.len > 16) { d4 = small_d; break; }
-    fr.v4 = build_lpm(ib, pb, r4[f], 32, d4);
-    fr.v6 = build_lpm(ib, pb, r6[f], 128, 16, v6wtb);
+    fr.v4 = build_lpm(ib, pb, r4[f], 32, d4, aux);
+    fr.v6 = build_lpm(ib, pb, r6[f], 128, 16, aux, v6wtb);
     if (fr.v6.wtab) im.v6w_fib = 1;
     fibs.push_back(fr);
     vrfkv.push_back(KV{s.vrf_id, 0, 0, f});
@@ -1325,7 +1408,7 @@ int build_image(const dp_tables_desc_t *d, BuiltImage &out, PfLineage *pf) {
     Mbi m{};
     if (gi < 0) return m;
     Group G;
-    memcpy(&G, ib.b.data() + C.group_recs + (uint64_t)gi * sizeof(Group), sizeof(Group));
+    memcpy(&G, ib.at(C.group_recs + (uint64_t)gi * sizeof(Group)), sizeof(Group));
     if (G.mode != DPD_GROUP_LIST || !G.f[G.lfield].root) return m;
     const FieldIdx &F = G.f[G.lfield];
     m.root = (uint32_t)F.root; m.blocks = (uint32_t)F.blocks; m.s0 = F.s0; m.kbits = F.kbits;
@@ -1337,7 +1420,7 @@ int build_image(const dp_tables_desc_t *d, BuiltImage &out, PfLineage *pf) {
     Mbi m{};
     if (gi < 0) return m;
     Group G;
-    memcpy(&G, ib.b.data() + C.group_recs + (uint64_t)gi * sizeof(Group), sizeof(Group));
+    memcpy(&G, ib.at(C.group_recs + (uint64_t)gi * sizeof(Group)), sizeof(Group));
     if (G.mode != DPD_GROUP_LIST || !G.f[G.lfield].root || G.lfield2 == DPD_NO_FIELD || !G.f[G.lfield2].root)
       return m;
     const FieldIdx &F = G.f[G.lfield2];
@@ -1421,7 +1504,7 @@ int build_image(const dp_tables_desc_t *d, BuiltImage &out, PfLineage *pf) {
     im.ff_remote[t].aux = ib.put(aux);
     for (auto &pa : ffr_aux[t]) {
       uint32_t v = pair_of(pa.second->vni_a, pa.second->action);
-      memcpy(ib.b.data() + pa.first, &v, 4);
+      memcpy(ib.at(pa.first), &v, 4);
     }
   }
   for (int ti : {0, 1, 4, 5})
@@ -1568,10 +1651,14 @@ int build_image(const dp_tables_desc_t *d, BuiltImage &out, PfLineage *pf) {
   mc->randomize = d->masq_randomize != 0;
   mc->seed = d->masq_seed;
   ib.alloc(64);
-  im.bytes = ib.b.size();
+  im.bytes = ib.size();
   // context records carry 32-bit image offsets (Mbi)
   if (im.bytes >= (1ull << 32)) return DP_ENOMEM;
   out.bytes.swap(ib.b);
+  out.holes.swap(ib.holes);
+  out.fib_builds.swap(fib_builds);
+  out.sort_us = (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(aux.sort).count();
+  out.paint_us = (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(aux.paint).count();
   out.im = im;
   out.pt_nodes = pb.nodes.size();
   out.masq = mc;

@@ -9,6 +9,7 @@
 
 #include "../../include/dpgpu.h"
 #include "dp_device.h"
+#include "dp_fibbuild.h"
 
 namespace dpd {
 
@@ -38,11 +39,32 @@ struct MasqConfig {
   }
 };
 
+// A region of the image the host reserved and did not fill: the device builds
+// it (DP_OPT_DEVICE_FIB).  Holes ascend and never touch.
+struct ImageHole {
+  uint64_t off, bytes;
+};
+// The lists one device-built DIR-24-8 FIB is made from (dp_fibbuild.h) and the
+// image offsets of its two holes (block16 is host-built zeros when there is
+// no block).
+struct FibBuild {
+  std::vector<dpb::Short> shorts;
+  std::vector<dpb::Long> longs;
+  std::vector<dpb::Block> blocks;
+  uint64_t direct = 0, block16 = 0;
+};
+
 struct BuiltImage {
-  std::vector<uint8_t> bytes;  // host copy of the device image
-  Image im;                    // offsets into `bytes`
+  // host copy of the device image -- without the holes: the bytes of image
+  // offset o are at o minus the holes below o (no hole unless build_image was
+  // asked for device FIBs: then `bytes` is the image)
+  std::vector<uint8_t> bytes;
+  std::vector<ImageHole> holes;
+  std::vector<FibBuild> fib_builds;
+  Image im;                    // image offsets; im.bytes counts the holes
   uint64_t pt_nodes = 0;
   std::shared_ptr<const MasqConfig> masq;  // never null after a successful build
+  uint64_t sort_us = 0, paint_us = 0;      // build_lpm: sort + dedupe + list prep; host table build
 };
 
 // The port-forwarding entries of a device's current generation (the lineage
@@ -58,7 +80,8 @@ struct PfLineage {
 
 // Validate + lower the descriptors; returns 0 or a negative errno.  `pf`:
 // the device's port-forwarding lineage, updated with the new rule set (only
-// when the build succeeds).
-int build_image(const dp_tables_desc_t *desc, BuiltImage &out, PfLineage *pf = nullptr);
+// when the build succeeds).  `device_fib`: v4 FIBs that take the DIR-24-8 form
+// get holes and build lists instead of host-built tables.
+int build_image(const dp_tables_desc_t *desc, BuiltImage &out, PfLineage *pf = nullptr, bool device_fib = false);
 
 }  // namespace dpd

@@ -692,6 +692,7 @@ extern "C" uint32_t dpw_sizeof(const char *name) {
       {"dp_flow_t", sizeof(dp_flow_t)}, {"dp_flow_info_t", sizeof(dp_flow_info_t)},
       {"dp_flow_filter_t", sizeof(dp_flow_filter_t)}, {"dp_flow_entry_t", sizeof(dp_flow_entry_t)},
       {"dp_mbuf_layout_t", sizeof(dp_mbuf_layout_t)}, {"dp_tx_port_t", sizeof(dp_tx_port_t)},
+      {"dp_publish_stats_t", sizeof(dp_publish_stats_t)},
   };
   for (auto &e : tab)
     if (strcmp(e.n, name) == 0) return e.s;

@@ -74,6 +74,18 @@ class GpuPathNf:
         A.check(self.lib.dp_tables_publish(self.ctx, tables_ptr), "dp_tables_publish", self.lib)
         self.data.genid = int(self.lib.dp_tables_genid(self.ctx))
 
+    def set_device_fib(self, on: bool) -> None:
+        """dp_ctx_set_option(DP_OPT_DEVICE_FIB): the publishes that follow build
+        the DIR-24-8 tables of large v4 FIBs on the device instead of uploading them."""
+        self.set_option(A.OPT_DEVICE_FIB, 1 if on else 0)
+
+    def publish_stats(self) -> np.ndarray:
+        """dp_tables_publish_stats: one A.PUBLISH_STATS record on this context's
+        last publish (FIBs built on the device, bytes uploaded, phase times)."""
+        st = np.zeros(1, dtype=A.PUBLISH_STATS)
+        A.check(self.lib.dp_tables_publish_stats(self.ctx, st.ctypes.data), "dp_tables_publish_stats", self.lib)
+        return st[0]
+
     def set_data(self, data: PipelineData) -> None:
         self.data = data
 

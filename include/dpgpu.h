@@ -649,7 +649,20 @@ enum dp_ctx_option {
      * dp_process_mbufs) ignore the option: their caller has the frames on the
      * host already.  0 (default), or no capture open: no launch, no
      * allocation. */
-    DP_OPT_CAPTURE = 4
+    DP_OPT_CAPTURE = 4,
+    /* 1: dp_tables_publish through this context builds the tables of every
+     * v4 FIB that takes the DIR-24-8 form (more than 65,536 v4 routes, next
+     * hops below 0xffff) on the device: the host neither fills nor uploads
+     * the 64 MiB direct table and the next-hop blocks, it uploads the rest of
+     * the image and a compact route list (16 B a route), and two kernels on a
+     * stream of the publish's own write the tables in place before the
+     * generation is swapped in ("Publish statistics" below reports what ran).
+     * The image -- layout and every byte -- is the host-built one, so the
+     * lookups do not change; the other table forms, v6 and the classifiers
+     * are host-built either way.  The publish takes 16 B a route of device
+     * memory more until it returns.  A failure leaves the current generation
+     * in place.  0 (default): the host builds and uploads everything. */
+    DP_OPT_DEVICE_FIB = 5
 };
 enum dp_host_path { DP_HOST_AUTO = 0, DP_HOST_COPY = 1, DP_HOST_ZERO_COPY = 2 };
 int dp_ctx_set_option(dp_ctx_t *ctx, int option, int64_t value);
@@ -1337,6 +1350,27 @@ int dp_tx_plan(dp_ctx_t *, const dp_pkt_out_t *out, uint32_t n, const uint32_t *
  * dp_mbuf_burst_out.  DP_EINVAL for an order[k] >= n (nothing is promised
  * about tx_mbufs then) or a NULL array with n_order > 0. */
 int dp_mbuf_burst_tx(void *const *mbufs, uint32_t n, const uint32_t *order, uint32_t n_order, void **tx_mbufs);
+
+/* ------------------------------------------------------------------------ */
+/* Publish statistics: what the context's last successful dp_tables_publish  */
+/* did and how long its phases took (host clock, microseconds; the device    */
+/* build by HIP events, nanoseconds).  DP_ENOTABLES before the context's     */
+/* first successful publish.                                                 */
+/* ------------------------------------------------------------------------ */
+typedef struct dp_publish_stats {
+    uint32_t device_fibs;   /* FIBs whose DIR-24-8 tables the device built (DP_OPT_DEVICE_FIB) */
+    uint32_t pad;
+    uint64_t image_bytes;   /* the image in device memory */
+    uint64_t upload_bytes;  /* bytes sent over the bus: the image (less the device-built regions) and the build lists */
+    uint64_t built_bytes;   /* bytes the build kernels wrote: direct tables and blocks */
+    uint64_t sort_us;       /* FIB routes: sort, duplicate pass, build lists */
+    uint64_t paint_us;      /* host-built FIB tables: direct tables, blocks, Poptrie */
+    uint64_t compile_us;    /* the rest of the table compile */
+    uint64_t upload_us;     /* device allocation and copies */
+    uint64_t kernel_ns;     /* the build kernels */
+    uint64_t total_us;      /* dp_tables_publish, entry to return */
+} dp_publish_stats_t;       /* 80 B */
+int dp_tables_publish_stats(const dp_ctx_t *ctx, dp_publish_stats_t *out);
 
 /* Introspection: bytes of the device table image and its parts (for
  * DESIGN.md / bench), and the last HIP error string. */

@@ -337,7 +337,7 @@ assert TX_PORT.itemsize == 24
 TX_MAX_PORTS = 62     # DP_TX_MAX_PORTS
 TX_PLAN_TILE = 2048   # dpt::kTile (csrc/dp_txplan.h): packets a workgroup of the plan takes
 # publish statistics (include/dpgpu.h "Publish statistics"): dp_publish_stats_t
-PUBLISH_STATS = np.dtype([("device_fibs", "<u4"), ("pad", "<u4"), ("image_bytes", "<u8"), ("upload_bytes", "<u8"),
+PUBLISH_STATS = np.dtype([("device_fibs", "<u4"), ("sorted_fibs", "<u4"), ("image_bytes", "<u8"), ("upload_bytes", "<u8"),
                           ("built_bytes", "<u8"), ("sort_us", "<u8"), ("paint_us", "<u8"), ("compile_us", "<u8"),
                           ("upload_us", "<u8"), ("kernel_ns", "<u8"), ("total_us", "<u8")])
 assert PUBLISH_STATS.itemsize == 80

@@ -47,6 +47,7 @@ extern "C" int dpk_capture_reset(void *state, hipStream_t stream);
 extern "C" hipError_t dpk_tx_plan(const dp_pkt_out_t *out, uint32_t n, const dpt::Ports *pl, void *scratch,
                                   uint32_t *order, dp_tx_port_t *ports, hipStream_t stream);
 extern "C" hipError_t dpk_fib_build(const dpb::Job *job, hipStream_t stream);
+extern "C" hipError_t dpk_fib_sort(const dps::SortJob *job, hipStream_t stream);
 extern "C" int dpk_vpc_stats(const dp_pkt_out_t *out, const dp_pkt_meta_t *meta, uint32_t n, void *table,
                              uint32_t max_blocks, hipStream_t stream);
 extern "C" int dpk_launch_pipeline(const uint8_t *img_base, const void *image_dev, uint8_t *buf,
@@ -339,7 +340,7 @@ struct dp_ctx {
   // publish: DP_OPT_DEVICE_FIB, the build kernels' stream and timing events
   // (created at the first device build), and the last successful publish's
   // record (dp_tables_publish_stats)
-  bool device_fib = false;
+  int device_fib = 0;  // DP_OPT_DEVICE_FIB: 0 off, 1 the device paints, 2 it also sorts and lists the routes
   hipStream_t fb_stream = nullptr;
   hipEvent_t fb_t0 = nullptr, fb_t1 = nullptr;
   dp_publish_stats_t pub_stats{};
@@ -806,7 +807,10 @@ int dp_ctx_destroy(dp_ctx_t *c) {
 // The device build of a publish (DP_OPT_DEVICE_FIB): the build lists of every
 // such FIB go into one temporary device buffer, the kernels of dp_fibbuild.hip
 // fill the image's holes on the context's build stream, and the call waits for
-// them.  The buffer is freed on every path.
+// them.  A FIB that comes as raw records (mode 2) has them uploaded instead;
+// the kernels of dp_fibsort.hip make its lists in the same buffer ahead of
+// the build, and the two counts the build is launched with are read back.
+// The buffer is freed on every path.
 static int fib_device_build(dp_ctx *c, uint8_t *img, const dpd::BuiltImage &bi, dp_publish_stats_t &st) {
   hipError_t e;
   if (!c->fb_stream && ((e = hipStreamCreateWithFlags(&c->fb_stream, hipStreamNonBlocking)) != hipSuccess ||
@@ -815,14 +819,22 @@ static int fib_device_build(dp_ctx *c, uint8_t *img, const dpd::BuiltImage &bi, 
   auto al = [](uint64_t n) { return (n + 255) & ~(uint64_t)255; };
   uint64_t need = 0;
   for (const dpd::FibBuild &fb : bi.fib_builds) {
+    const bool raw = !fb.raw.empty();
     for (const dpb::Block &b : fb.blocks)
       if (b.count > dpb::kBlockRoutes || (uint64_t)b.first + b.count > fb.longs.size() || b.slot >= dpb::kSlots)
         return fail(DP_EINVAL, "device FIB build: bad block list");
-    if (fb.shorts.empty() || fb.direct + 4ull * dpb::kSlots > bi.im.bytes ||
-        fb.block16 + 512ull * fb.blocks.size() > bi.im.bytes)
+    const uint64_t n_blocks = raw ? fb.n_blocks : fb.blocks.size();
+    if ((raw ? fb.raw.size() > dps::kMaxRoutes || (uint64_t)fb.raw_short + fb.raw_long != fb.raw.size() || !fb.raw_short
+             : fb.shorts.empty()) ||
+        fb.direct + 4ull * dpb::kSlots > bi.im.bytes || fb.block16 + 512ull * n_blocks > bi.im.bytes)
       return fail(DP_EINVAL, "device FIB build: bad regions");
-    need += al(sizeof(dpb::Short) * fb.shorts.size()) + al(sizeof(dpb::Block) * fb.blocks.size()) +
-            al(sizeof(dpb::Long) * fb.longs.size());
+    if (raw)
+      need += 2 * al(sizeof(dps::Raw) * fb.raw.size()) + al(4 * dps::scratch_words((uint32_t)fb.raw.size())) +
+              al(sizeof(dps::Counts)) + al(sizeof(dpb::Short) * fb.raw_short) + al(sizeof(dpb::Block) * n_blocks) +
+              al(sizeof(dpb::Long) * fb.raw_long);
+    else
+      need += al(sizeof(dpb::Short) * fb.shorts.size()) + al(sizeof(dpb::Block) * fb.blocks.size()) +
+              al(sizeof(dpb::Long) * fb.longs.size());
   }
   const auto t_lists = std::chrono::steady_clock::now();
   uint8_t *lists = nullptr;
@@ -830,37 +842,76 @@ static int fib_device_build(dp_ctx *c, uint8_t *img, const dpd::BuiltImage &bi, 
   int rc = 0;
   uint64_t o = 0;
   std::vector<dpb::Job> jobs;
+  std::vector<dps::SortJob> sorts;  // one a job; n == 0: the host made the lists
   for (const dpd::FibBuild &fb : bi.fib_builds) {
     dpb::Job j{};
-    auto put = [&](const void *p, uint64_t n) -> uint8_t * {
+    dps::SortJob s{};
+    auto put = [&](const void *p, uint64_t n, uint64_t room) -> uint8_t * {
       uint8_t *d = lists + o;
       if (!rc && n && (e = hipMemcpy(d, p, n, hipMemcpyHostToDevice)) != hipSuccess)
         rc = fail(DP_EIO, "device FIB build: upload lists", e);
-      o += al(n);
+      o += al(room);
       st.upload_bytes += n;
       return d;
     };
-    j.shorts = reinterpret_cast<const dpb::Short *>(put(fb.shorts.data(), sizeof(dpb::Short) * fb.shorts.size()));
-    j.blocks = reinterpret_cast<const dpb::Block *>(put(fb.blocks.data(), sizeof(dpb::Block) * fb.blocks.size()));
-    j.longs = reinterpret_cast<const dpb::Long *>(put(fb.longs.data(), sizeof(dpb::Long) * fb.longs.size()));
+    if (!fb.raw.empty()) {
+      const uint64_t bytes = sizeof(dps::Raw) * fb.raw.size();
+      s.n = (uint32_t)fb.raw.size();
+      s.a = reinterpret_cast<dps::Raw *>(put(fb.raw.data(), bytes, bytes));
+      s.b = reinterpret_cast<dps::Raw *>(put(nullptr, 0, bytes));
+      s.scratch = reinterpret_cast<uint32_t *>(put(nullptr, 0, 4 * dps::scratch_words(s.n)));
+      s.counts = reinterpret_cast<dps::Counts *>(put(nullptr, 0, sizeof(dps::Counts)));
+      s.shorts = reinterpret_cast<dpb::Short *>(put(nullptr, 0, sizeof(dpb::Short) * fb.raw_short));
+      s.blocks = reinterpret_cast<dpb::Block *>(put(nullptr, 0, sizeof(dpb::Block) * fb.n_blocks));
+      s.longs = reinterpret_cast<dpb::Long *>(put(nullptr, 0, sizeof(dpb::Long) * fb.raw_long));
+      s.cap_short = fb.raw_short;
+      s.cap_long = fb.raw_long;
+      s.cap_blocks = fb.n_blocks;
+      j.shorts = s.shorts;
+      j.blocks = s.blocks;
+      j.longs = s.longs;
+      j.n_blocks = fb.n_blocks;  // n_short: from the device
+      st.sorted_fibs++;
+    } else {
+      j.shorts = reinterpret_cast<const dpb::Short *>(put(fb.shorts.data(), sizeof(dpb::Short) * fb.shorts.size(), sizeof(dpb::Short) * fb.shorts.size()));
+      j.blocks = reinterpret_cast<const dpb::Block *>(put(fb.blocks.data(), sizeof(dpb::Block) * fb.blocks.size(), sizeof(dpb::Block) * fb.blocks.size()));
+      j.longs = reinterpret_cast<const dpb::Long *>(put(fb.longs.data(), sizeof(dpb::Long) * fb.longs.size(), sizeof(dpb::Long) * fb.longs.size()));
+      j.n_short = (uint32_t)fb.shorts.size();
+      j.n_blocks = (uint32_t)fb.blocks.size();
+    }
     j.direct = reinterpret_cast<uint32_t *>(img + fb.direct);
     j.block16 = reinterpret_cast<uint16_t *>(img + fb.block16);
-    j.n_short = (uint32_t)fb.shorts.size();
-    j.n_blocks = (uint32_t)fb.blocks.size();
     jobs.push_back(j);
-    st.built_bytes += 4ull * dpb::kSlots + 512ull * fb.blocks.size();
+    sorts.push_back(s);
+    st.built_bytes += 4ull * dpb::kSlots + 512ull * j.n_blocks;
   }
   st.upload_us += (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_lists).count();
   if (!rc) {
+    const char *what = "device FIB build: kernels";
     e = hipEventRecord(c->fb_t0, c->fb_stream);
-    for (size_t k = 0; k < jobs.size() && e == hipSuccess; k++) e = dpk_fib_build(&jobs[k], c->fb_stream);
-    if (e == hipSuccess) e = hipEventRecord(c->fb_t1, c->fb_stream);
+    for (size_t k = 0; k < jobs.size() && e == hipSuccess && !rc; k++) {
+      if (sorts[k].n) {
+        dps::Counts got{};
+        if ((e = dpk_fib_sort(&sorts[k], c->fb_stream)) != hipSuccess ||
+            (e = hipMemcpyAsync(&got, sorts[k].counts, sizeof got, hipMemcpyDeviceToHost, c->fb_stream)) != hipSuccess ||
+            (e = hipStreamSynchronize(c->fb_stream)) != hipSuccess)
+          break;
+        // the image was laid out for the host's block count
+        if (got.n_blocks != jobs[k].n_blocks || !got.n_short || got.n_short > sorts[k].cap_short || got.n_long > sorts[k].cap_long) {
+          rc = fail(DP_EIO, "device FIB build: the device's route lists do not match the host's block count");
+          break;
+        }
+        jobs[k].n_short = got.n_short;
+      }
+      e = dpk_fib_build(&jobs[k], c->fb_stream);
+    }
+    if (e == hipSuccess && !rc) e = hipEventRecord(c->fb_t1, c->fb_stream);
     // whatever was enqueued reads the lists: wait before they go
     const hipError_t es = hipStreamSynchronize(c->fb_stream);
     if (e == hipSuccess) e = es;
     float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->fb_t0, c->fb_t1);
-    if (e != hipSuccess) rc = fail(DP_EIO, "device FIB build: kernels", e);
+    if (e == hipSuccess && !rc) e = hipEventElapsedTime(&ms, c->fb_t0, c->fb_t1);
+    if (e != hipSuccess && !rc) rc = fail(DP_EIO, what, e);
     st.kernel_ns = (uint64_t)((double)ms * 1e6);
   }
   (void)hipFree(lists);
@@ -1614,8 +1665,8 @@ int dp_ctx_set_option(dp_ctx_t *c, int option, int64_t value) {
     return 0;
   }
   if (option == DP_OPT_DEVICE_FIB) {
-    if (value != 0 && value != 1) return fail(DP_EINVAL, "device FIB build: 0 or 1");
-    c->device_fib = value != 0;
+    if (value < 0 || value > 2) return fail(DP_EINVAL, "device FIB build: 0, 1 or 2");
+    c->device_fib = (int)value;
     return 0;
   }
   return fail(DP_EINVAL, "unknown option");

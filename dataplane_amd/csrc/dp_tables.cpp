@@ -265,6 +265,19 @@ void add_v6_window(ImgBuf &ib, PtBuilder &pb, const std::vector<PRoute> &uniq, L
   L.wbits = (uint32_t)c;
 }
 
+// The two regions of a device-built DIR-24-8 FIB, where build_lpm puts them.
+Lpm reserve_regions(ImgBuf &ib, uint64_t n_blocks, FibBuild &fb) {
+  Lpm L{};
+  if (!n_blocks) L.blocks = ib.put(std::vector<uint16_t>(256, 0));
+  else L.blocks = ib.reserve(512 * n_blocks);
+  L.direct = ib.reserve(4ull << 24);
+  L.dbits = 24;
+  L.width = 32;
+  fb.direct = L.direct;
+  fb.block16 = L.blocks;
+  return L;
+}
+
 // DIR-24-8 in device form (DP_OPT_DEVICE_FIB): the direct table and the blocks
 // are reserved at the offsets build_lpm puts them at and left to the kernels
 // of dp_fibbuild.hip; one pass over the sorted unique routes writes their lists.
@@ -285,15 +298,38 @@ Lpm reserve_dir248(ImgBuf &ib, const std::vector<PRoute> &uniq, FibBuild &fb) {
     fb.blocks.back().count++;
     fb.longs.push_back(kbits(r.key, 24, 8) | (uint32_t)r.len << 8 | r.nh << 16);
   }
-  Lpm L{};
-  if (fb.blocks.empty()) L.blocks = ib.put(std::vector<uint16_t>(256, 0));
-  else L.blocks = ib.reserve(512 * (uint64_t)fb.blocks.size());
-  L.direct = ib.reserve(4ull << 24);
-  L.dbits = 24;
-  L.width = 32;
-  fb.direct = L.direct;
-  fb.block16 = L.blocks;
-  return L;
+  return reserve_regions(ib, fb.blocks.size(), fb);
+}
+
+// A v4 FIB's routes as the device route sort takes them (DP_OPT_DEVICE_FIB = 2,
+// dp_fibsort.h): 8-byte records in insertion order, and one bit per /24 that
+// holds a route of length 25..32 -- the bitmap's popcount is the block count,
+// all the image layout needs to know of the sorted list.
+struct RawFib {
+  std::vector<dps::Raw> raw;
+  std::vector<uint64_t> long24;  // 2^24 bits
+  uint32_t n_short = 0, n_long = 0;
+  void add(uint32_t addr, uint32_t len, uint32_t nh) {
+    raw.push_back(dps::pack(addr, len, nh));
+    if (len > 24) {
+      long24[addr >> 14] |= 1ull << ((addr >> 8) & 63u);
+      n_long++;
+    } else {
+      n_short++;
+    }
+  }
+};
+
+// DIR-24-8 left whole to the device: the same two regions at the same offsets
+// as reserve_dir248, and the records instead of the lists.
+Lpm reserve_dir248_raw(ImgBuf &ib, RawFib &rf, FibBuild &fb) {
+  uint64_t n_blocks = 0;
+  for (uint64_t w : rf.long24) n_blocks += (uint64_t)__builtin_popcountll(w);
+  fb.raw.swap(rf.raw);
+  fb.raw_short = rf.n_short;
+  fb.raw_long = rf.n_long;
+  fb.n_blocks = (uint32_t)n_blocks;
+  return reserve_regions(ib, n_blocks, fb);
 }
 
 // Build one FIB/family LPM; routes must include a /0.
@@ -880,7 +916,7 @@ void be_words(const dp_prefix_t &p, uint32_t w[4]) {
 
 }  // namespace
 
-int build_image(const dp_tables_desc_t *d, BuiltImage &out, PfLineage *pf, bool device_fib) {
+int build_image(const dp_tables_desc_t *d, BuiltImage &out, PfLineage *pf, int device_fib) {
   LpmAux aux;
   std::vector<FibBuild> fib_builds;
   if (device_fib) aux.dev = &fib_builds;
@@ -999,12 +1035,47 @@ int build_image(const dp_tables_desc_t *d, BuiltImage &out, PfLineage *pf, bool 
     r4[f].push_back(PRoute{0, 0, drop_nh});
     r6[f].push_back(PRoute{0, 0, drop_nh});
   }
+  // Device route sort (mode 2): a FIB that will take the DIR-24-8 form on the
+  // device (build_lpm's test: more than 65,536 v4 routes with the implicit /0,
+  // every next hop that can survive below 0xffff -- the implicit /0's unless
+  // an inserted /0 replaces it) keeps no PRoute: its v4 routes are packed into
+  // raw records as they pass by.  Counted first, so that a FIB is one or the
+  // other from its first route on.
+  const auto t_pack = std::chrono::steady_clock::now();
+  std::vector<RawFib> raw4(d->n_fibs);
+  bool packing = false;
+#if !defined(DP_DIR16) && !defined(DP_NO_DIR248)
+  if (device_fib == 2) {
+    std::vector<uint64_t> n4(d->n_fibs, 1);
+    std::vector<uint32_t> top(d->n_fibs, 0);
+    std::vector<uint8_t> has0(d->n_fibs, 0);
+    for (uint64_t i = 0; i < d->n_routes; i++) {
+      const dp_route_t &r = d->routes[i];
+      if (r.fib >= d->n_fibs || r.prefix.family != 4) continue;
+      n4[r.fib]++;
+      top[r.fib] = std::max(top[r.fib], r.nh);
+      if (r.prefix.len == 0) has0[r.fib] = 1;
+    }
+    for (uint32_t f = 0; f < d->n_fibs; f++) {
+      if (n4[f] <= 65536 || n4[f] > dps::kMaxRoutes || (has0[f] ? top[f] : std::max(top[f], drop_nh)) >= 0xffffu) continue;
+      raw4[f].raw.reserve(n4[f]);
+      raw4[f].long24.assign((size_t)1 << 18, 0);
+      raw4[f].add(0, 0, std::min(drop_nh, 0xffffu));  // (0xffff: an inserted /0 comes behind it)
+      packing = true;
+    }
+  }
+#endif
   for (uint64_t i = 0; i < d->n_routes; i++) {
     const dp_route_t &r = d->routes[i];
     if (r.fib >= d->n_fibs || r.nh >= d->n_route_nhs || !valid_prefix(r.prefix)) return DP_EINVAL;
+    if (r.prefix.family == 4 && !raw4[r.fib].long24.empty()) {
+      raw4[r.fib].add(be32(r.prefix.addr), r.prefix.len, r.nh);
+      continue;
+    }
     PRoute p{key128(r.prefix.family, r.prefix.addr), r.prefix.len, r.nh};
     (r.prefix.family == 4 ? r4 : r6)[r.fib].push_back(p);
   }
+  if (packing) aux.sort += std::chrono::steady_clock::now() - t_pack;
   PtBuilder pb;
   std::vector<FibRec> fibs;
   std::vector<KV> vrfkv, vnikv;
@@ -1042,7 +1113,12 @@ int build_image(const dp_tables_desc_t *d, BuiltImage &out, PfLineage *pf, bool 
     else
       for (const PRoute &p : r4[f])
         if (p.len > 16) { d4 = small_d; break; }
-    fr.v4 = build_lpm(ib, pb, r4[f], 32, d4, aux);
+    if (!raw4[f].long24.empty()) {
+      fib_builds.emplace_back();
+      fr.v4 = reserve_dir248_raw(ib, raw4[f], fib_builds.back());
+    } else {
+      fr.v4 = build_lpm(ib, pb, r4[f], 32, d4, aux);
+    }
     fr.v6 = build_lpm(ib, pb, r6[f], 128, 16, aux, v6wtb);
     if (fr.v6.wtab) im.v6w_fib = 1;
     fibs.push_back(fr);

@@ -10,6 +10,7 @@
 #include "../../include/dpgpu.h"
 #include "dp_device.h"
 #include "dp_fibbuild.h"
+#include "dp_fibsort.h"
 
 namespace dpd {
 
@@ -46,12 +47,17 @@ struct ImageHole {
 };
 // The lists one device-built DIR-24-8 FIB is made from (dp_fibbuild.h) and the
 // image offsets of its two holes (block16 is host-built zeros when there is
-// no block).
+// no block).  With the device route sort (DP_OPT_DEVICE_FIB = 2) the lists
+// stay empty: `raw` holds the FIB's v4 routes in insertion order, the implicit
+// /0 first (dp_fibsort.h), with how many of them are of length <= 24 and
+// longer, and `n_blocks` the /24s that hold a longer one.
 struct FibBuild {
   std::vector<dpb::Short> shorts;
   std::vector<dpb::Long> longs;
   std::vector<dpb::Block> blocks;
   uint64_t direct = 0, block16 = 0;
+  std::vector<dps::Raw> raw;
+  uint32_t raw_short = 0, raw_long = 0, n_blocks = 0;
 };
 
 struct BuiltImage {
@@ -64,7 +70,8 @@ struct BuiltImage {
   Image im;                    // image offsets; im.bytes counts the holes
   uint64_t pt_nodes = 0;
   std::shared_ptr<const MasqConfig> masq;  // never null after a successful build
-  uint64_t sort_us = 0, paint_us = 0;      // build_lpm: sort + dedupe + list prep; host table build
+  // build_lpm: sort + dedupe + list prep (device route sort: the pass that packs the records); host table build
+  uint64_t sort_us = 0, paint_us = 0;
 };
 
 // The port-forwarding entries of a device's current generation (the lineage
@@ -80,8 +87,9 @@ struct PfLineage {
 
 // Validate + lower the descriptors; returns 0 or a negative errno.  `pf`:
 // the device's port-forwarding lineage, updated with the new rule set (only
-// when the build succeeds).  `device_fib`: v4 FIBs that take the DIR-24-8 form
-// get holes and build lists instead of host-built tables.
-int build_image(const dp_tables_desc_t *desc, BuiltImage &out, PfLineage *pf = nullptr, bool device_fib = false);
+// when the build succeeds).  `device_fib` (the DP_OPT_DEVICE_FIB mode), 1: v4
+// FIBs that take the DIR-24-8 form get holes and build lists instead of
+// host-built tables; 2: holes and their unsorted route records.
+int build_image(const dp_tables_desc_t *desc, BuiltImage &out, PfLineage *pf = nullptr, int device_fib = 0);
 
 }  // namespace dpd

@@ -74,10 +74,12 @@ class GpuPathNf:
         A.check(self.lib.dp_tables_publish(self.ctx, tables_ptr), "dp_tables_publish", self.lib)
         self.data.genid = int(self.lib.dp_tables_genid(self.ctx))
 
-    def set_device_fib(self, on: bool) -> None:
+    def set_device_fib(self, on) -> None:
         """dp_ctx_set_option(DP_OPT_DEVICE_FIB): the publishes that follow build
-        the DIR-24-8 tables of large v4 FIBs on the device instead of uploading them."""
-        self.set_option(A.OPT_DEVICE_FIB, 1 if on else 0)
+        the DIR-24-8 tables of large v4 FIBs on the device instead of uploading them.
+        `on`: a bool, or the option's integer mode (2: the device also sorts and
+        lists the routes)."""
+        self.set_option(A.OPT_DEVICE_FIB, int(on))
 
     def publish_stats(self) -> np.ndarray:
         """dp_tables_publish_stats: one A.PUBLISH_STATS record on this context's

@@ -661,7 +661,21 @@ enum dp_ctx_option {
      * lookups do not change; the other table forms, v6 and the classifiers
      * are host-built either way.  The publish takes 16 B a route of device
      * memory more until it returns.  A failure leaves the current generation
-     * in place.  0 (default): the host builds and uploads everything. */
+     * in place.
+     * 2: as 1, and the device also sorts and lists such a FIB's routes (at
+     * most 2^26 of them; a larger FIB is built as under 1).  The host neither
+     * sorts them nor removes duplicate prefixes: it validates and packs them in
+     * insertion order at 8 B a route (address, length, next hop), uploads
+     * that, and kernels ahead of the two above sort the records stably by
+     * (address, length), keep the last insert of a prefix and write the
+     * route lists the build reads, which never leave the device.  The image
+     * is still the host-built one byte for byte; the device's block count is
+     * checked against the host's before anything is written (DP_EIO, nothing
+     * published).  The publish takes at most 37 B a route of device memory
+     * more until it returns (the records twice, 0.5 B of histograms, the
+     * lists at up to 20 B).  dp_publish_stats_t.sorted_fibs counts these FIBs.
+     * 0 (default): the host builds and uploads everything.  Another value is
+     * DP_EINVAL. */
     DP_OPT_DEVICE_FIB = 5
 };
 enum dp_host_path { DP_HOST_AUTO = 0, DP_HOST_COPY = 1, DP_HOST_ZERO_COPY = 2 };
@@ -1359,7 +1373,7 @@ int dp_mbuf_burst_tx(void *const *mbufs, uint32_t n, const uint32_t *order, uint
 /* ------------------------------------------------------------------------ */
 typedef struct dp_publish_stats {
     uint32_t device_fibs;   /* FIBs whose DIR-24-8 tables the device built (DP_OPT_DEVICE_FIB) */
-    uint32_t pad;
+    uint32_t sorted_fibs;   /* those of them whose route list the device also sorted and listed (mode 2; else 0) */
     uint64_t image_bytes;   /* the image in device memory */
     uint64_t upload_bytes;  /* bytes sent over the bus: the image (less the device-built regions) and the build lists */
     uint64_t built_bytes;   /* bytes the build kernels wrote: direct tables and blocks */

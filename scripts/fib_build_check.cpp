@@ -7,8 +7,12 @@
 // host-built image byte for byte.  Tables: C2's from the workload generator
 // (argv[1] v4 routes, default 1M); with a second argument also a dense tile,
 // full /25../32 nests, blocks at slots 0 and 2^24 - 1 and in adjacent slots, a
-// duplicate prefix and routes on tile borders.  Prints the host phase times of
-// both forms.  Build and run from the repository root, e.g. under sanitizers:
+// duplicate prefix and routes on tile borders, and the order and duplicate
+// shapes of tests/test_gpu_fib_device_sort.py.  The route-sort form
+// (DP_OPT_DEVICE_FIB = 2) must reserve the same image from unsorted records,
+// and a host restatement of the kernels of dp_fibsort.hip must turn them into
+// the host's three lists element for element.  Prints the host phase times of
+// the forms.  Build and run from the repository root, e.g. under sanitizers:
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined scripts/fib_build_check.cpp \
 //       dataplane_amd/csrc/dp_tables.cpp -o /tmp/fib_build_check -lpthread
 //   /tmp/fib_build_check 200000 extra
@@ -71,6 +75,75 @@ static void emu_blocks(const dpd::FibBuild &fb, uint32_t *direct, uint16_t *b16)
   }
 }
 
+// The kernels of dp_fibsort.hip restated (DP_OPT_DEVICE_FIB = 2): the same
+// tiles, digit-major histograms, scan, stable scatter (a record's in-tile rank
+// is the count of its digit before it in tile order, which is what the ballots
+// and wave counters compute), flags, list positions, parent search and block
+// counts.  Returns the lists made from the raw records.
+static dpd::FibBuild emu_sort(const dpd::FibBuild &in) {
+  using namespace dps;
+  constexpr uint32_t kSortTile = dps::kTile;
+  const uint32_t n = (uint32_t)in.raw.size(), tiles = tiles_of(n);
+  std::vector<Raw> a(in.raw), b(n);
+  std::vector<uint32_t> sc(scratch_words(n));
+  auto scan = [&](uint32_t m) {
+    uint32_t run = 0;
+    for (uint32_t i = 0; i < m; i++) { const uint32_t x = sc[i]; sc[i] = run; run += x; }
+    sc[m] = run;
+  };
+  for (uint32_t p = 0; p < kPasses; p++) {
+    const uint32_t nd = kMask[p] + 1;
+    std::fill(sc.begin(), sc.end(), 0);
+    for (uint32_t i = 0; i < n; i++) sc[((uint32_t)(a[i] >> kShift[p]) & kMask[p]) * tiles + i / kSortTile]++;
+    scan(nd * tiles);
+    for (uint32_t t = 0; t < tiles; t++) {
+      uint32_t seen[kDigits] = {};
+      for (uint32_t i = t * kSortTile; i < n && i < (t + 1) * kSortTile; i++) {
+        const uint32_t d = (uint32_t)(a[i] >> kShift[p]) & kMask[p];
+        b[sc[d * tiles + t] + seen[d]++] = a[i];
+      }
+    }
+    a.swap(b);
+  }
+  auto flags = [&](uint32_t i) { return classify(i ? a[i - 1] : 0, a[i], i + 1 < n ? a[i + 1] : 0, i, n); };
+  std::fill(sc.begin(), sc.end(), 0);
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t f = flags(i), t = i / kSortTile;
+    sc[t] += f & kIsShort, sc[tiles + t] += (f & kIsLong) >> 1, sc[2 * tiles + t] += f >> 2;
+  }
+  scan(3 * tiles);
+  dpd::FibBuild out;
+  const uint32_t n_short = sc[tiles], n_long = sc[2 * tiles] - n_short, n_blocks = sc[3 * tiles] - sc[2 * tiles];
+  if (n_short > in.raw_short || n_long > in.raw_long || n_blocks != in.n_blocks) { printf("counts outside the host's bounds\n"); exit(1); }
+  out.shorts.resize(n_short), out.longs.resize(n_long), out.blocks.resize(n_blocks);
+  for (uint32_t t = 0; t < tiles; t++) {
+    uint32_t ps = sc[t], pl = sc[tiles + t] - n_short, pb = sc[2 * tiles + t] - sc[2 * tiles];
+    for (uint32_t i = t * kSortTile; i < n && i < (t + 1) * kSortTile; i++) {
+      const uint32_t f = flags(i), ad = addr_of(a[i]), len = len_of(a[i]), nh = nh_of(a[i]);
+      if (f & kIsHead) out.blocks.at(pb++) = Block{ad >> 8, pl, 0, 0};
+      if (f & kIsShort) { out.shorts.at(ps) = Short{ad >> 8, len, nh, ps}; ps++; }
+      if (f & kIsLong) out.longs.at(pl++) = (ad & 0xffu) | len << 8 | nh << 16;
+    }
+  }
+  auto skey = [&](uint32_t i) { return (uint64_t)out.shorts.at(i).slot << 6 | out.shorts[i].len; };
+  for (uint32_t me = 0; me < n_short; me++) {
+    const uint32_t slot = out.shorts[me].slot, len = out.shorts[me].len;
+    uint32_t parent = me, hi = me;
+    for (uint32_t step = 0; step < 24 && step < len && hi; step++) {
+      const uint32_t L = len - 1 - step;
+      const uint64_t target = (uint64_t)(slot >> (24 - L) << (24 - L)) << 6 | L;
+      uint32_t lo = 0, h = hi;
+      for (uint32_t s = 0; s < 32 && lo < h; s++) { const uint32_t mid = lo + ((h - lo) >> 1); if (skey(mid) < target) lo = mid + 1; else h = mid; }
+      if (lo < hi && skey(lo) == target) { parent = lo; break; }
+      hi = lo;
+    }
+    out.shorts[me].parent = parent;
+  }
+  for (uint32_t k = 0; k < n_blocks; k++) out.blocks[k].count = (k + 1 < n_blocks ? out.blocks[k + 1].first : n_long) - out.blocks[k].first;
+  out.direct = in.direct, out.block16 = in.block16;
+  return out;
+}
+
 static void add(dpw_workload *w, uint32_t fib, uint32_t addr, int len, uint32_t nh) {
   dp_route_t r{};
   r.prefix.family = 4;
@@ -97,20 +170,39 @@ int main(int argc, char **argv) {
   if (dpw_build(&c, &w)) return 2;
   if (extra) {
     uint32_t k = 1;
-    const uint32_t base = 0x2c400000;  // a /14: the dense tile
+    const uint32_t F = w->routes[0].fib;  // the FIB that holds the generator's v4 routes: the DIR-24-8 one
+    const uint32_t base = 0x2c400000;     // a /14: the dense tile
     for (int len = 14; len <= 24; len++)
-      for (uint32_t i = 0; i < (1u << (len - 14)); i++) add(w, 0, base + (i << (32 - len)), len, k++);
+      for (uint32_t i = 0; i < (1u << (len - 14)); i++) add(w, F, base + (i << (32 - len)), len, k++);
     for (uint32_t s : {0u, 0xffffffu, 0x123456u, 0x123457u})
-      for (int len = 25; len <= 32; len++) add(w, 0, (s << 8) | 0x80 | (s & 1 ? 0x55 : 0), len, k++);
-    add(w, 0, 0x12345600, 25, k++);
-    add(w, 0, 0x12345600, 24, k++);
-    add(w, 0, 0x12345600, 24, k++);  // duplicate: the last wins
-    add(w, 0, 0, 0, k++);
-    for (int len : {8, 12, 16, 20, 24}) add(w, 0, 0x0a0b0c00, len, k++);
-    add(w, 0, 0x0a0c0000, 16, k++);
-    add(w, 0, 0x4ffffc00 + 0x300, 24, k++);  // a tile's last slot
-    add(w, 0, 0x50000000, 24, k++);          // a tile's first slot
-    add(w, 0, 0x50000000, 14, k++);
+      for (int len = 25; len <= 32; len++) add(w, F, (s << 8) | 0x80 | (s & 1 ? 0x55 : 0), len, k++);
+    add(w, F, 0x12345600, 25, k++);
+    add(w, F, 0x12345600, 24, k++);
+    add(w, F, 0x12345600, 24, k++);  // duplicate: the last wins
+    add(w, F, 0, 0, k++);
+    for (int len : {8, 12, 16, 20, 24}) add(w, F, 0x0a0b0c00, len, k++);
+    add(w, F, 0x0a0c0000, 16, k++);
+    add(w, F, 0x4ffffc00 + 0x300, 24, k++);  // a tile's last slot
+    add(w, F, 0x50000000, 24, k++);          // a tile's first slot
+    add(w, F, 0x50000000, 14, k++);
+    for (int i = 5000; i-- > 0;) add(w, F, 0x3c000000 + ((uint32_t)i << 8), 24, k++);   // descending
+    for (int len = 8; len <= 32; len++) add(w, F, 0x0b000000, len, k++);                // one address, every length
+    for (int len = 25; len <= 32; len++)                                                // a full /24 of 510 long routes
+      for (uint32_t i = 0; i < (1u << (len - 24)); i++) add(w, F, 0x3d000000 + (i << (32 - len)), len, k++);
+    add(w, F, 0x3d000100 + 77, 32, k++);                                                // next to a /24 holding one
+    std::vector<dp_route_t> all;                                                        // one prefix 5,000 times,
+    const size_t every = w->routes.size() / 5000;                                       // through the whole order
+    for (size_t i = 0; i < w->routes.size(); i++) {
+      all.push_back(w->routes[i]);
+      if (i % every == 0) {
+        dp_route_t r = w->routes.back();
+        put32(r.prefix.addr, 0x3e000000 + (i % (3 * every) ? 0 : 0x80));  // (and a second one, long)
+        r.prefix.len = i % (3 * every) ? 20 : 25;
+        r.nh = (uint32_t)(i / every) % (uint32_t)w->nhs.size();
+        all.push_back(r);
+      }
+    }
+    w->routes.swap(all);
     w->desc.routes = w->routes.data();
     w->desc.n_routes = w->routes.size();
   }
@@ -149,6 +241,25 @@ int main(int argc, char **argv) {
       if (full[i] != host.bytes[i] && bad++ < 5) printf("differs at %zu: %02x vs %02x\n", i, full[i], host.bytes[i]);
     printf("%s (%zu bytes differ)\n", bad ? "MISMATCH" : "identical", bad);
     if (bad) return 7;
+    // mode 2: the same layout from unsorted records, and the restated sort
+    // kernels' lists against the host's, element for element
+    dpd::BuiltImage raw;
+    t = std::chrono::steady_clock::now();
+    if (dpd::build_image(d, raw, nullptr, 2)) return 8;
+    printf("raw form: total %lu us pack %lu paint %lu\n", us(t), raw.sort_us, raw.paint_us);
+    if (raw.im.bytes != dev.im.bytes || memcmp(&raw.im, &dev.im, sizeof raw.im) || raw.bytes != dev.bytes ||
+        raw.fib_builds.size() != dev.fib_builds.size()) { printf("raw form: image differs\n"); return 9; }
+    for (size_t k = 0; k < raw.fib_builds.size(); k++) {
+      const dpd::FibBuild &rb = raw.fib_builds[k], &hb = dev.fib_builds[k];
+      if (rb.raw.empty() || !rb.shorts.empty() || rb.direct != hb.direct || rb.block16 != hb.block16) { printf("raw form: fib %zu\n", k); return 10; }
+      const dpd::FibBuild made = emu_sort(rb);
+      const bool same = made.shorts.size() == hb.shorts.size() && made.longs == hb.longs && made.blocks.size() == hb.blocks.size() &&
+                        !memcmp(made.shorts.data(), hb.shorts.data(), sizeof(Short) * hb.shorts.size()) &&
+                        !memcmp(made.blocks.data(), hb.blocks.data(), sizeof(Block) * hb.blocks.size());
+      printf("fib %zu: %zu raw routes -> %zu short %zu long %zu blocks: lists %s\n", k, rb.raw.size(), made.shorts.size(),
+             made.longs.size(), made.blocks.size(), same ? "identical" : "MISMATCH");
+      if (!same) return 11;
+    }
   }
   dpw_free(w);
   return 0;

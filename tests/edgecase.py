@@ -626,7 +626,10 @@ def edge_frames(n: int, seed: int):
 
 
 def pack_burst(frames, headroom: int = A.HEADROOM):
-    """Lay frames out in one buffer (16-byte aligned slots, headroom in front)."""
+    """Lay frames out in one zero-filled buffer: every frame starts on a
+    16-byte boundary with `headroom` bytes in front, and headroom, gaps and
+    tail are zeros.  Frames at other start residues, packed tightly with
+    random fill: placement.pack_at."""
     offs, total = [], 0
     for fr, *_ in frames:
         total += headroom
